@@ -11,8 +11,16 @@ pupil samples and traces them through every surface to the image plane, writing
 x, y, z, L, M, N, i, opd to HBM: exactly RealRayTracer.trace's work
 (real_ray_tracer.py:37-97) for one (field, wavelength) on 1M rays.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--no-cpu]
-                    [--config {1,2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--config {1,2,3,4,5}]
+                    [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, ramps the clock, warms up, times the K steps and prints the result
+line. --dump-outputs DIR then writes what the last timed step computed (the arrays a caller
+of the timed path receives) as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared output for output. --full adds the measurements that
+take runs of their own: the CPU baseline leg (cpu_baseline; --no-cpu skips it), config 5's
+live adjoint-kernel time (roofline.kernel_ms) and, at N > 1, config 4's trace-alone time
+and gather report.
 
 N > 1: launched by torch.distributed.run, one process per GPU; every rank traces its
 own 1M-ray shard (weak scaling, no collective on the data path); the elapsed time is
@@ -148,7 +156,8 @@ def config1(args, dev, rank, world, torch):
         kernel="trace_closed_kernel<F_GEN|F_SPOT> + spot_dev + spot_final (graph)",
         launches=3,
         bytes_per_launch=None, flops_per_ray=None, pmc_file=None, rays=n, state=state,
-        spot=True, data="synthetic (the reference's uniform 128 pupil grid)", ramp_steps=24000)
+        spot=True, data="synthetic (the reference's uniform 128 pupil grid)", ramp_steps=24000,
+        outputs=lambda: {**_ray_outputs(out), "spot_stats": state["stats"]})
 
 
 def config2(args, dev, rank, world, torch):
@@ -180,7 +189,8 @@ def config2(args, dev, rank, world, torch):
             "parallelism": f"dp{world} (ray shards, no collective)"},
         kernel="trace_closed_kernel<F_GEN> (ort_trace_pupil)", launches=1,
         bytes_per_launch=R * (16 + 64), flops_per_ray=flops, pmc_file="hbm_traffic.json",
-        rays=R, ramp_steps=max(64, 90_000_000_000 // max(1, R * S)))
+        rays=R, ramp_steps=max(64, 90_000_000_000 // max(1, R * S)),
+        outputs=lambda: _ray_outputs(out))
 
 
 def config3(args, dev, rank, world, torch):
@@ -225,7 +235,8 @@ def config3(args, dev, rank, world, torch):
                 "parallelism": f"dp{world} (ray shards, no collective)"},
         kernel="trace_kernel<F_GEN|KM_EVEN> (ort_trace_pupil)", launches=1,
         bytes_per_launch=n_p * 16 + n * 64, flops_per_ray=flops, pmc_file="hbm_traffic_c3.json",
-        compute_pmc_file="r05_config3_pmc_compute.json", rays=n)
+        compute_pmc_file="r05_config3_pmc_compute.json", rays=n,
+        outputs=lambda: _ray_outputs(out))
 
 
 def config4(args, dev, rank, world, torch):
@@ -339,7 +350,11 @@ def config4(args, dev, rank, world, torch):
         kernel="trace_closed_kernel<F_GEN> (ort_trace_pupil)", launches=1,
         bytes_per_launch=n * (16 + 64), flops_per_ray=None, pmc_file="hbm_traffic_c4.json",
         rays=n, extra=gather_report, trace_timer=trace_ms if world > 1 else None,
-        traffic_scale=n / (n_p * len(pairs)))  # the PMC pass traced all pairs on one GPU
+        traffic_scale=n / (n_p * len(pairs)),  # the PMC pass traced all pairs on one GPU
+        # N > 1: rank 0's gathered image (x, y of every pair in the reference's order)
+        outputs=(lambda: _ray_outputs(out)) if gather is None else (
+            lambda: {"image_x": gather.planes[0].reshape(-1),
+                     "image_y": gather.planes[1].reshape(-1)}))
 
 
 def config5(args, dev, rank, world, torch):
@@ -381,9 +396,9 @@ def config5(args, dev, rank, world, torch):
         def loss_fn():
             return RayOperand.rms_spot_size(lens, -1, 0.0, 1.0, R, 0.587, d)
 
-        return lens, opt, loss_fn
+        return lens, opt, loss_fn, leaves
 
-    lens, opt, loss_fn = problem(use_graph)
+    lens, opt, loss_fn, leaves = problem(use_graph)
     state = {}
 
     def eager_step_of(opt, loss_fn, keep):
@@ -397,11 +412,13 @@ def config5(args, dev, rank, world, torch):
         return step
 
     eager_step = eager_step_of(opt, loss_fn, True)
-    # the backward's device time (vjp_timer) is measured on eager steps of a SECOND copy of
-    # the problem: eager steps of the captured lens itself would overwrite the replays'
-    # Newton flags and reuse the autograd nodes the capture's outputs keep alive
-    _, opt_t, loss_t = problem(False) if use_graph else (lens, opt, loss_fn)
-    timer_step = eager_step_of(opt_t, loss_t, False) if use_graph else eager_step
+    # --full: the backward's device time (vjp_timer) is measured on eager steps of a SECOND
+    # copy of the problem: eager steps of the captured lens itself would overwrite the
+    # replays' Newton flags and reuse the autograd nodes the capture's outputs keep alive
+    timer_step = None
+    if args.full:
+        _, opt_t, loss_t, _ = problem(False) if use_graph else (lens, opt, loss_fn, leaves)
+        timer_step = eager_step_of(opt_t, loss_t, False) if use_graph else eager_step
 
     # the whole optimisation step -- coefficient patch, taped trace with its device-verified
     # Newton rounds, rms_spot, the adjoint VJP, the fused Adam update -- as ONE HIP graph
@@ -435,7 +452,14 @@ def config5(args, dev, rank, world, torch):
                               if use_graph else "eager (torch ops + ctypes launches)"},
         kernel="adj_kernel<KM_ZERN, 2> (ort_trace_pupil_vjp, adjoint mode)", launches=None,
         bytes_per_launch=None, flops_per_ray=None, pmc_file="hbm_traffic_c5.json", rays=R,
-        state=state, vjp_timer=vjp_timer, eager_step=timer_step, ramp_steps=720,
+        state=state, vjp_timer=vjp_timer if args.full else None, eager_step=timer_step,
+        ramp_steps=720,
+        # what the optimisation step hands back: the loss, the updated coefficients of the
+        # three mirrors and their gradients
+        outputs=lambda: {"loss": state["loss"],
+                         **{f"coefficients_{k}": t.detach() for k, t in enumerate(leaves)},
+                         **{f"grad_{k}": t.grad for k, t in enumerate(leaves)
+                            if t.grad is not None}},
         # the taped forward writes the tape, the adjoint only reads it: per traced surface the
         # incoming ray and t (7 rows) plus, for a Newton surface, the min(U, 4) iterates it
         # replays (ort_sweep.h adj_ray), with U the verified schedule -- read after the run
@@ -491,6 +515,37 @@ def vjp_timer(step, steps, torch):
     return sum(spans) / len(spans)
 
 
+def _ray_outputs(out):
+    """The traced rays a caller of trace_pupil receives (RealRays on the device)."""
+    from optiland_pr_amd import _abi
+
+    return {a: getattr(out, a) for a in _abi.RAY_FIELDS}
+
+
+DUMP_BYTES = 48_000_000  # budget of --dump-outputs (float64 on disk), all arrays together
+
+
+def _dump_outputs(path, outputs, torch):
+    """Write the device tensors `outputs` (name -> tensor) as <path>/<name>.npy, float64.
+    Above DUMP_BYTES in all, every array keeps the same fraction of its leading axis: a
+    sorted sample drawn by numpy's default_rng(0), so arrays of one length (the fields of
+    the traced rays) keep the same rows, and the same rows on every run."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 8 for t in outputs.values())
+    picks = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if total > DUMP_BYTES and t.dim() > 0 and t.shape[0] > 1:
+            n = t.shape[0]
+            if n not in picks:
+                k = max(1, int(n * DUMP_BYTES / total))
+                idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+                picks[n] = torch.as_tensor(idx, device=t.device)
+            t = t.index_select(0, picks[n])
+        np.save(os.path.join(path, f"{name}.npy"),
+                np.asarray(t.cpu().numpy(), dtype=np.float64))
+
+
 CONFIGS = {1: config1, 2: config2, 3: config3, 4: config4, 5: config5}
 
 
@@ -501,7 +556,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=1_000_000)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the measurements that need runs of their own: the CPU "
+                         "baseline leg, config 5's live adjoint-kernel time, config 4's "
+                         "trace-alone time and gather report at N > 1")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the rows when "
+                         "the arrays exceed 48 MB in all)")
     ap.add_argument("--newton-mode", default="reference", choices=["reference", "wave"],
                     help="config 3: the reference's global Newton stop rule (exact) or the "
                          "per-wavefront stop (within the Newton tolerance)")
@@ -534,10 +598,10 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # the CPU baseline runs first, before anything touches the GPU (its worker processes
-    # are forked from this one)
+    # --full: the CPU baseline runs first, before anything touches the GPU (its worker
+    # processes are forked from this one)
     cpu_line = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu_line = _cpu_baseline(args)
 
     import torch
@@ -609,12 +673,17 @@ def main():
             w.state["check"]()
         loss = w.state.get("loss")
         final_loss = None if loss is None else float(loss)
-    extra = w.extra() if getattr(w, "extra", None) else None  # every rank (collectives)
-    if getattr(w, "vjp_timer", None):
-        w.vjp_ms = w.vjp_timer(getattr(w, "eager_step", w.step), max(3, min(args.steps, 20)),
-                               torch)
-    if getattr(w, "trace_timer", None):
-        kern_ms = w.trace_timer(max(3, min(args.steps, 20)))
+    # the last timed step's outputs, before any further step overwrites them
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, w.outputs(), torch)
+    extra = None
+    if args.full:  # measurements with runs of their own, after the timed region
+        extra = w.extra() if getattr(w, "extra", None) else None  # every rank (collectives)
+        if getattr(w, "vjp_timer", None):
+            w.vjp_ms = w.vjp_timer(getattr(w, "eager_step", w.step),
+                                   max(3, min(args.steps, 20)), torch)
+        if getattr(w, "trace_timer", None):
+            kern_ms = w.trace_timer(max(3, min(args.steps, 20)))
 
     if rank == 0:
         line = {
@@ -637,7 +706,7 @@ def main():
                        "kernel_time": "HIP events at both ends of the timed region / steps"
                        + ("; roofline kernel_ms = the trace launch alone (events around "
                           "each launch, after the timed region: the step also gathers)"
-                          if getattr(w, "trace_timer", None) else "")},
+                          if args.full and getattr(w, "trace_timer", None) else "")},
         }
         if w.flops_per_ray is not None:
             line["roofline_fp64"] = _roofline_fp64(w, kern_ms)

@@ -4,6 +4,7 @@
 -m gpu runs on the MI355X box: the HIP path against the oracle and the golden vectors.
 """
 
+import glob
 import json
 import os
 import sys
@@ -29,4 +30,12 @@ def golden_index():
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False))
+    """The arrays of <name>.npz, joined with those a case too large for one file keeps split
+    along their leading axis in <name>.part0.npz, <name>.part1.npz, ..."""
+    g = dict(np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False))
+    parts = [np.load(p, allow_pickle=False)
+             for p in sorted(glob.glob(os.path.join(GOLDEN, f"{name}.part[0-9].npz")))]
+    if parts:
+        for k in parts[0].files:
+            g[k] = np.concatenate([p[k] for p in parts])
+    return g

@@ -731,7 +731,13 @@ def generate_case(name, builder, fields, wavelengths, dist, num):
         semi_aperture=[None if s.semi_aperture is None else float(np.ravel(s.semi_aperture)[0])
                        for s in sg.surfaces],
     )
+    # the per-surface records go into part files of their own, split by pair, so that every
+    # committed file stays well under 1 MiB (tests/conftest.py load_golden joins them)
+    rec = arrays.pop("records", None)
     np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **arrays)
+    if rec is not None:
+        for k, part in enumerate(np.array_split(rec, 3)):
+            np.savez_compressed(os.path.join(HERE, f"{name}.part{k}.npz"), records=part)
     return meta
 
 

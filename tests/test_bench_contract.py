@@ -66,3 +66,27 @@ def test_config5_tape_bytes_follow_the_schedule():
     lens._lowered = {"k": SimpleNamespace(table=table, sched_cache={"_default": U})}
     assert bench._tape_read_bytes(lens, 1_000_000) == (7 * S + int((U > 0).sum())) * 8 * 1_000_000
     assert bench._tape_read_bytes(lens, 1_000_000) == 31 * 8 * 1_000_000
+
+
+def test_dump_outputs_samples_the_same_rows_within_the_budget(tmp_path):
+    """--dump-outputs: arrays over the byte budget keep a fixed seeded sample of their rows,
+    the same rows for arrays of one length and on every call; small arrays are whole."""
+    import numpy as np
+    import torch
+
+    n = bench.DUMP_BYTES // 8  # two such arrays: twice the budget
+    x = torch.arange(n, dtype=torch.float64)
+    outs = {"x": x, "y": 2 * x + 1, "loss": torch.tensor(0.25, dtype=torch.float64)}
+    bench._dump_outputs(str(tmp_path / "a"), outs, torch)
+    bench._dump_outputs(str(tmp_path / "b"), outs, torch)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in outs}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in outs}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES <= 64_000_000
+    assert a["x"].size >= n // 2 - 1 and np.all(np.diff(a["x"]) > 0)
+    assert np.array_equal(a["y"], 2 * a["x"] + 1)  # the same rows of both
+    assert all(np.array_equal(a[k], b[k]) for k in outs)
+    assert a["loss"].shape == () and a["loss"] == 0.25
+    small = {"x": x[:1001], "y": x[:1001] * 3}
+    bench._dump_outputs(str(tmp_path / "c"), small, torch)
+    assert np.array_equal(np.load(tmp_path / "c" / "y.npy"), small["y"].numpy())

@@ -21,8 +21,8 @@ for step in "$@"; do
     tests) run pytest_gpu 900 python -m pytest tests -m gpu -q -x -rf ;;
     testsall) run pytest_gpu 900 python -m pytest tests -m gpu -q -rf ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    benchq) run bench 600 python bench.py --steps 20 --warmup 3 ;;
+    bench) run bench 600 python bench.py --full ;;
+    benchq) run bench 600 python bench.py --full --steps 20 --warmup 3 ;;
     prof) cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
           run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python3 bench.py --no-cpu --steps 20 --warmup 3 ;;
     pmc) cd /tmp && export TMPDIR=/tmp && cd - >/dev/null

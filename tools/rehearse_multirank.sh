@@ -10,5 +10,5 @@ run() { local n=$1; shift; echo "== $n"; timeout -k 10 300 "$@" > gpurun_out/$n.
 for c in 2 4 5; do
   run rehearse_c$c python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port $((29500 + c)) bench.py --gpus 2 --steps 5 \
-    --warmup 2 --config $c --backend gloo
+    --warmup 2 --config $c --backend gloo --full
 done
