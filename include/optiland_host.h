@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ORT_HOST_ABI_VERSION 2
+#define ORT_HOST_ABI_VERSION 3
 
 int ort_host_abi_version(void);
 
@@ -78,6 +78,17 @@ int ort_host_trace_pupil_vjp(const ort_lens* lens, const double* px, const doubl
 int ort_host_rms_spot(const double* x, const double* y, int64_t n, double* stats, double* rms);
 int ort_host_rms_spot_vjp(const double* x, const double* y, int64_t n, const double* stats,
                           const double* grad_out, double* gx, double* gy);
+
+/* ort_huygens_psf on host memory (v3): the Huygens-Fresnel sum of
+ * psf/huygens_fresnel_strategies.py:97-172 with the kernel's own term (csrc/ort_huygens.h)
+ * and its summation order -- per image point the pupil in chunks of ORT_HUYGENS_CHUNK, each
+ * from zero in index order, the chunk sums added in chunk order -- OpenMP over the image
+ * points (the value does not depend on the thread count). Same argument checks as
+ * ort_huygens_psf, no workspace. */
+int ort_host_huygens_psf(const double* ix, const double* iy, const double* iz, int64_t n_image,
+                         const double* px, const double* py, const double* pz,
+                         const double* amp, const double* opd_mm, int64_t n_pupil,
+                         double wavelength_mm, double rp, double* psf);
 
 /* threads used by the calls (OpenMP; <= 0: the OpenMP default) */
 void ort_host_set_threads(int32_t n);

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ORT_ABI_VERSION 20
+#define ORT_ABI_VERSION 21
 #define ORT_MAX_SURFACES 64
 
 /* ---- geometry kinds ----------------------------------- */
@@ -873,6 +873,30 @@ int ort_wavefront_opd(const ort_rays* rays, const double* px, const double* py, 
                       const ort_wavefront_ref* ref, double* opd_wv, double* pupil_x,
                       double* pupil_y, double* pupil_z, void* workspace,
                       int64_t workspace_size, double* sums, void* stream);
+
+/* ---- Huygens-Fresnel PSF (psf/huygens_fresnel_strategies.py:97-172, v21) -------------
+ * The reference's Numba double loop over image points x pupil points: psf[p] =
+ * |sum_j amp_j Q_obliq exp(i k (R_pj - opd_j)) / R_pj|^2, fp64 throughout, the phase
+ * reduced in cycles before the sincos (csrc/ort_huygens.h). The pupil is summed in fixed
+ * chunks of ORT_HUYGENS_CHUNK points (one partial complex sum per image point and chunk in
+ * the workspace), the partials added in chunk order by a second launch: no atomics, the
+ * bits do not depend on the device, the grid or how the image points are shaped. */
+#define ORT_HUYGENS_CHUNK 512
+
+/* Bytes of device workspace ort_huygens_psf needs (< 0: ORT_ERR_ARG). */
+int64_t ort_huygens_workspace_size(int64_t n_image, int64_t n_pupil);
+
+/* ix, iy, iz: the n_image image points (device, global frame); px, py, pz, amp, opd_mm: the
+ * n_pupil exit-pupil points, their amplitudes and OPD in mm (device); rp: the radius of the
+ * exit-pupil reference sphere. Writes psf[n_image] = the raw |field|^2 (the caller
+ * normalises). n_pupil == 0 writes zeros; n_image == 0 launches nothing. ORT_ERR_ARG for
+ * negative counts, null pointers of a positive count, wavelength_mm <= 0 or a short
+ * workspace. Two launches on `stream`, no synchronisation. */
+int ort_huygens_psf(const double* ix, const double* iy, const double* iz, int64_t n_image,
+                    const double* px, const double* py, const double* pz,
+                    const double* amp, const double* opd_mm, int64_t n_pupil,
+                    double wavelength_mm, double rp, double* psf, void* workspace,
+                    int64_t workspace_size, void* stream);
 
 /* Ray generation only (ray_generator.py:28-106): fills rays_out from pupil points. */
 int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,

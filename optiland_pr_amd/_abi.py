@@ -9,7 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-ABI_VERSION = 20
+ABI_VERSION = 21
+HUYGENS_CHUNK = 512  # ORT_HUYGENS_CHUNK: pupil points per partial sum of ort_huygens_psf
 VJP_UNROLLED = 0
 VJP_ADJOINT = 1
 AP_RADIAL = 1

@@ -155,7 +155,8 @@ EXPORTS = ("ort_abi_version", "ort_trace_sequential", "ort_trace_pupil", "ort_tr
            "ort_rms_spot_workspace_size", "ort_rms_spot", "ort_rms_spot_vjp",
            "ort_wavefront_workspace_size", "ort_wavefront_opd", "ort_patch_zernike",
            "ort_patch_zernike_ptrs", "ort_newton_finish", "ort_adam_patch_zernike",
-           "ort_rms_finish", "ort_newton_finish_rms")
+           "ort_rms_finish", "ort_newton_finish_rms", "ort_huygens_workspace_size",
+           "ort_huygens_psf")
 
 _lib = None
 
@@ -267,6 +268,13 @@ def load(path: str | None = None):
                                       P(ort_wavefront_ref), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_void_p]
+    lib.ort_huygens_workspace_size.restype = C.c_int64
+    lib.ort_huygens_workspace_size.argtypes = [C.c_int64, C.c_int64]
+    lib.ort_huygens_psf.restype = C.c_int
+    lib.ort_huygens_psf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p]
     v = lib.ort_abi_version()
     if v != _abi.ABI_VERSION:
         raise NativeLibraryError(f"ABI version mismatch: library {v}, host {_abi.ABI_VERSION}")
@@ -277,8 +285,9 @@ def load(path: str | None = None):
 
 HOST_EXPORTS = ("ort_host_abi_version", "ort_host_trace_sequential",
                 "ort_host_trace_sequential_vjp", "ort_host_trace_pupil", "ort_host_trace_pupil_vjp",
-                "ort_host_rms_spot", "ort_host_rms_spot_vjp", "ort_host_set_threads")
-HOST_ABI_VERSION = 2  # include/optiland_host.h ORT_HOST_ABI_VERSION
+                "ort_host_rms_spot", "ort_host_rms_spot_vjp", "ort_host_set_threads",
+                "ort_host_huygens_psf")
+HOST_ABI_VERSION = 3  # include/optiland_host.h ORT_HOST_ABI_VERSION
 
 _host = None
 
@@ -320,6 +329,11 @@ def load_host(path: str | None = None):
                                           C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ort_host_set_threads.restype = None
     lib.ort_host_set_threads.argtypes = [C.c_int32]
+    lib.ort_host_huygens_psf.restype = C.c_int
+    lib.ort_host_huygens_psf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                         C.c_void_p]
     v = lib.ort_host_abi_version()
     if v != HOST_ABI_VERSION:
         raise NativeLibraryError(f"host ABI version mismatch: library {v}, host {HOST_ABI_VERSION}")

@@ -39,6 +39,29 @@ def resolve_fields(optic, fields):
     raise TypeError("Fields must be a string ('all') or a list.")
 
 
+def get_working_FNO(optic, field, wavelength):
+    """utils.py:14-64: the working F-number of one field point and wavelength from the
+    chief ray and four marginal rays (traced on the device; the five direction cosines
+    come to the host, where the reference's NumPy expressions run as they are)."""
+    MAX_FNUM = 10000.0
+    Hx, Hy = field
+    n = optic.image_surface.material_post.n(wavelength)
+    Px = np.array([0, 0, 0, 1, -1])
+    Py = np.array([0, 1, -1, 0, 0])
+    rays = optic.trace_generic(Hx=Hx, Hy=Hy, Px=Px, Py=Py, wavelength=wavelength)
+    L, M, N = torch.stack([rays.L, rays.M, rays.N]).cpu().numpy()
+    dot = L[0] * L[1:] + M[0] * M[1:] + N[0] * N[1:]
+    dot = np.clip(dot, -1.0, 1.0)
+    angles = np.arccos(dot)
+    avg_NA_squared = np.mean((n * np.sin(angles)) ** 2)
+    fno = np.inf if avg_NA_squared <= 0 else 1 / (2 * np.sqrt(avg_NA_squared))
+    if fno > MAX_FNUM:
+        fno = MAX_FNUM
+    if np.isnan(fno):
+        raise ValueError("Working F/# could not be calculated due to raytrace errors.")
+    return fno
+
+
 def resolve_wavelengths(optic, wavelengths):
     """utils.py:67-88."""
     if isinstance(wavelengths, str):
@@ -55,7 +78,16 @@ def resolve_wavelengths(optic, wavelengths):
 def localize_points(x, y, z, surface):
     """visualization/system/utils.py:16-46 (transform, is_global=True): apply the surface's
     localize ops to points (direction cosines zero)."""
-    for kind, p in surface.geometry.cs.localize_ops():
+    return _apply_cs_ops(x, y, z, surface.geometry.cs.localize_ops())
+
+
+def globalize_points(x, y, z, surface):
+    """transform(..., is_global=False): the surface's globalize ops applied to local points."""
+    return _apply_cs_ops(x, y, z, surface.geometry.cs.globalize_ops())
+
+
+def _apply_cs_ops(x, y, z, ops):
+    for kind, p in ops:
         if kind == _abi.CS_TRANSLATE:
             x, y, z = x + p[0], y + p[1], z + p[2]
         elif kind == _abi.CS_ROT_X:

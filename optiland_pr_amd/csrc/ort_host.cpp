@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ort_huygens.h"
 #include "ort_sweep.h"
 
 namespace {
@@ -578,6 +579,37 @@ int ort_host_rms_spot_vjp(const double* x, const double* y, int64_t n, const dou
   for (int64_t k = 0; k < n; ++k) {
     gx[k] = (x[k] - mx) * s;
     gy[k] = (y[k] - my) * s;
+  }
+  return ORT_OK;
+}
+
+// HuygensPSF's summation (psf/huygens_fresnel_strategies.py:97-172) on host memory: the
+// kernel's term and its order of additions (ort_huygens.h, ort_k_huygens.hip), the image
+// points split over OpenMP threads.
+int ort_host_huygens_psf(const double* ix, const double* iy, const double* iz, int64_t n_image,
+                         const double* px, const double* py, const double* pz,
+                         const double* amp, const double* opd_mm, int64_t n_pupil,
+                         double wavelength_mm, double rp, double* psf) {
+  if (n_image < 0 || n_pupil < 0 || !(wavelength_mm > 0.0)) return ORT_ERR_ARG;
+  if (n_image > 0 && (!ix || !iy || !iz || !psf)) return ORT_ERR_ARG;
+  if (n_pupil > 0 && (!px || !py || !pz || !amp || !opd_mm)) return ORT_ERR_ARG;
+  const double inv_wl = 1.0 / wavelength_mm, inv_rp = 1.0 / rp;
+  // (one thread below kParMin terms, as the ray phases)
+  const int nt = n_image < 2 ? 1 : threads_for(n_image * std::max<int64_t>(n_pupil, 1));
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int64_t p = 0; p < n_image; ++p) {
+    double re = 0.0, im = 0.0;
+    int64_t j0 = 0;
+    do {  // (an empty pupil: one empty chunk, as the kernel's grid)
+      const int64_t j1 = std::min<int64_t>(j0 + ORT_HUYGENS_CHUNK, n_pupil);
+      double cr, ci;
+      ort::huygens_chunk(ix[p], iy[p], iz[p], px, py, pz, amp, opd_mm, j0, j1, inv_wl, inv_rp,
+                         cr, ci);
+      re += cr;
+      im += ci;
+      j0 = j1;
+    } while (j0 < n_pupil);
+    psf[p] = re * re + im * im;
   }
   return ORT_OK;
 }

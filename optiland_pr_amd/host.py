@@ -228,3 +228,15 @@ def rms_spot_vjp(x, y, stats, g):
     rc = lib.ort_host_rms_spot_vjp(_p(x), _p(y), x.numel(), _p(stats), _p(g), _p(gx), _p(gy))
     _native.check(rc, "ort_host_rms_spot_vjp")
     return gx, gy
+
+
+def huygens_psf(image, pupil, wavelength_mm, rp):
+    """ort_host_huygens_psf: raw |field|^2 [n_image] of contiguous float64 CPU tensors
+    (image = x, y, z; pupil = x, y, z, amp, opd in mm)."""
+    lib = _native.load_host()
+    psf = torch.empty(image[0].numel(), dtype=torch.float64)
+    rc = lib.ort_host_huygens_psf(*(_p(t) for t in image), image[0].numel(),
+                                  *(_p(t) for t in pupil), pupil[0].numel(),
+                                  float(wavelength_mm), float(rp), _p(psf))
+    _native.check(rc, "ort_host_huygens_psf")
+    return psf

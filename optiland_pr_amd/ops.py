@@ -38,6 +38,11 @@ source (host.py, liboptiland_host.so, include/optiland_host.h) on a HostLens han
 its VJP on the host too. Neither falls back to the other: the dispatcher picks the kernel
 by the tensors' device, and a handle of the other kind raises. trace_pupil and rms_spot
 are CUDA-only.
+
+ort::huygens_psf(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_mm,
+wavelength_mm, rp) -> psf is HuygensPSF's summation (psf/huygens_fresnel_strategies.py:97-172,
+ort_huygens_psf) on both keys; it has no autograd formula yet and refuses inputs that require
+grad.
 """
 
 from __future__ import annotations
@@ -965,3 +970,90 @@ def _rms_spot_vjp_cpu(x, y, stats, g):
 def _(x, y, stats, g):
     return (x.new_empty(x.numel(), dtype=torch.float64),
             y.new_empty(y.numel(), dtype=torch.float64))
+
+
+# --------------------------------------------------------------------------------------
+# ort::huygens_psf -- HuygensPSF's summation (psf/huygens_fresnel_strategies.py:97-172)
+# --------------------------------------------------------------------------------------
+def _check_huygens_inputs(image, pupil, wavelength_mm):
+    """The kernels read every array as doubles of one device: three image arrays of one
+    size, five pupil arrays of one size."""
+    for t in (*image, *pupil):
+        if t.dtype != torch.float64:
+            raise ValueError(f"ort::huygens_psf: every tensor must be float64 (got {t.dtype})")
+        if t.device != image[0].device:
+            raise ValueError(f"ort::huygens_psf: tensors on {image[0].device} and {t.device}")
+    if any(t.shape != image[0].shape for t in image):
+        raise ValueError("ort::huygens_psf: image_x, image_y, image_z of different shapes")
+    if any(t.numel() != pupil[0].numel() for t in pupil):
+        raise ValueError("ort::huygens_psf: pupil arrays of different sizes")
+    if not wavelength_mm > 0.0:
+        raise ValueError(f"ort::huygens_psf: wavelength_mm must be positive (got {wavelength_mm})")
+
+
+def _flat(ts):
+    return [t.detach().reshape(-1).contiguous() for t in ts]
+
+
+@torch.library.custom_op("ort::huygens_psf", mutates_args=(), device_types="cuda")
+def huygens_psf(image_x: torch.Tensor, image_y: torch.Tensor, image_z: torch.Tensor,
+                pupil_x: torch.Tensor, pupil_y: torch.Tensor, pupil_z: torch.Tensor,
+                amp: torch.Tensor, opd_mm: torch.Tensor, wavelength_mm: float,
+                rp: float) -> torch.Tensor:
+    """ort_huygens_psf: the raw |field|^2 at every image point (any shape; the output takes
+    it) of the Huygens-Fresnel sum over the exit-pupil points -- one fused fp64 kernel over
+    (image tile, pupil chunk) and a fixed-order sum of the chunk partials on the current
+    stream, no host synchronisation. Not differentiable (yet): a requires_grad input
+    raises NotImplementedError."""
+    from .raytrace import _ptr, _stream_handle
+
+    lib = _native.load()
+    image, pupil = (image_x, image_y, image_z), (pupil_x, pupil_y, pupil_z, amp, opd_mm)
+    _check_huygens_inputs(image, pupil, wavelength_mm)
+    fi, fp = _flat(image), _flat(pupil)
+    n_i, n_p = fi[0].numel(), fp[0].numel()
+    size = int(lib.ort_huygens_workspace_size(n_i, n_p))
+    _native.check(size if size < 0 else 0, "ort_huygens_workspace_size")
+    ws = torch.empty(max(size, 8), dtype=torch.uint8, device=image_x.device)
+    psf = torch.empty(n_i, dtype=torch.float64, device=image_x.device)
+    rc = lib.ort_huygens_psf(*(_ptr(t) for t in fi), n_i, *(_ptr(t) for t in fp), n_p,
+                             float(wavelength_mm), float(rp), _ptr(psf), _ptr(ws), size,
+                             _stream_handle())
+    _native.check(rc, "ort_huygens_psf")
+    return psf.reshape(image_x.shape)
+
+
+@huygens_psf.register_kernel("cpu")
+def _huygens_psf_cpu(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_mm,
+                     wavelength_mm, rp):
+    """The CPU dispatch key: the same term and summation order in the host library."""
+    from . import host
+
+    image, pupil = (image_x, image_y, image_z), (pupil_x, pupil_y, pupil_z, amp, opd_mm)
+    _check_huygens_inputs(image, pupil, wavelength_mm)
+    return host.huygens_psf(_flat(image), _flat(pupil), wavelength_mm, rp).reshape(image_x.shape)
+
+
+@huygens_psf.register_fake
+def _(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_mm, wavelength_mm, rp):
+    _check_huygens_inputs((image_x, image_y, image_z), (pupil_x, pupil_y, pupil_z, amp, opd_mm),
+                          wavelength_mm)
+    return image_x.new_empty(image_x.shape, dtype=torch.float64)
+
+
+_HUYGENS_NO_GRAD = ("ort::huygens_psf is not differentiable: autograd through the "
+                    "Huygens-Fresnel PSF is not implemented (detach the inputs)")
+
+
+def _huygens_setup(ctx, inputs, output):
+    # refuse here, in the forward: a PSF that silently dropped its graph would give a loss
+    # built on it a zero gradient
+    if any(ctx.needs_input_grad):
+        raise NotImplementedError(_HUYGENS_NO_GRAD)
+
+
+def _huygens_backward(ctx, grad):
+    raise NotImplementedError(_HUYGENS_NO_GRAD)
+
+
+huygens_psf.register_autograd(_huygens_backward, setup_context=_huygens_setup)
