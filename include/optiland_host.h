@@ -73,8 +73,8 @@ int ort_host_trace_pupil_vjp(const ort_lens* lens, const double* px, const doubl
                              double* grad);
 
 /* ort_rms_spot / ort_rms_spot_vjp on host memory (v2): RayOperand.rms_spot_size
- * (optimization/operand/ray.py:300-340), stats = n, mean x, mean y, rms, max radius; sums in
- * index order. */
+ * (optimization/operand/ray.py:300-340), stats = n, mean x, mean y, rms, max radius; pairwise
+ * sums in a fixed order (n = 0: count 0, the rest NaN). */
 int ort_host_rms_spot(const double* x, const double* y, int64_t n, double* stats, double* rms);
 int ort_host_rms_spot_vjp(const double* x, const double* y, int64_t n, const double* stats,
                           const double* grad_out, double* gx, double* gy);

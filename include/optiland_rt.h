@@ -771,8 +771,9 @@ int ort_material_nk(const ort_lens* lens, int32_t mat, const double* w, int64_t 
  * out[pair][5] = { count, centroid x, centroid y (mean of the pair's points),
  * rms radius, max radius } with both radii about the centroid of the field's ref_wl
  * pair (spot_diagram.py:_center_spots). NaN points propagate as in NumPy; a pair without
- * points gives NaN statistics. Deterministic: every reduction runs in a fixed order,
- * no atomics. */
+ * points gives NaN statistics (count 0; every pair when n_pupil = 0, which runs one empty
+ * chunk), and a ref_wl pair without points gives its whole field NaN radii. Deterministic:
+ * every reduction runs in a fixed order, no atomics. */
 typedef struct ort_spot_layout {
   int64_t n_pupil;            /* rays per pair                                        */
   int32_t n_fields;
@@ -809,7 +810,8 @@ int ort_trace_spot(const ort_lens* lens, const double* px, const double* py,
  * rms = sqrt(mean((x - mean x)^2 + (y - mean y)^2)) over all n points (no intensity mask),
  * two passes in a fixed order (the spot-statistics kernels with one pair). stats (device
  * double[5]) = { n, mean x, mean y, rms, max radius }; rms (device double, nullable) gets
- * the rms again as its own scalar (the autograd op's output). Three launches.
+ * the rms again as its own scalar (the autograd op's output). Three launches. n = 0: one
+ * empty chunk, stats = { 0, NaN, NaN, NaN, NaN } and *rms = NaN (the vjp launches nothing).
  * ort_rms_spot_vjp: gx[i] = g (x_i - mean x) / (n rms), gy likewise, g = *grad_out (a
  * device scalar, read on the device: no host synchronisation). One launch. */
 int64_t ort_rms_spot_workspace_size(int64_t n);
@@ -831,7 +833,10 @@ int ort_rms_finish(const double* part, int64_t n_rows, double* stats, double* rm
  *            frame); the caller sums them over the ranks (all_reduce) -> sums1;
  *   phase 2: the centroid of each field's ref_wl pair from the reduced sums1, then
  *            out[pair][3] = { sum of (x - cx)^2 + (y - cy)^2, max radius, NaN flag } of
- *            this rank's points; the caller reduces SUM, MAX, MAX over the ranks.
+ *            this rank's points; the caller reduces SUM, MAX, MAX over the ranks. A NaN
+ *            radius sets the flag and leaves the max (the max of the other points); a
+ *            slice without points reports { 0, 0, 0 }: that the whole spot is empty shows
+ *            only in the reduced count, which the caller tests as below.
  * Then, as spot_diagram.py:317-357 forms them: centroid = sum / count, rms radius =
  * sqrt(sum r^2 / count), geometric radius = max radius (NaN when the flag is set or the
  * spot is empty). workspace: ort_spot_workspace_size(layout) bytes. */

@@ -295,6 +295,18 @@ void vjp_chunks(const KArgs& a, const JArgs& j, std::vector<double>& part, int64
 
 }  // namespace
 
+// sum of term(k), lo <= k < hi: halves down to runs of at most 8 terms added in order
+template <class F>
+static double pairwise_sum(int64_t lo, int64_t hi, const F& term) {
+  if (hi - lo <= 8) {
+    double s = 0.0;
+    for (int64_t k = lo; k < hi; ++k) s += term(k);
+    return s;
+  }
+  const int64_t mid = lo + (hi - lo) / 2;
+  return pairwise_sum(lo, mid, term) + pairwise_sum(mid, hi, term);
+}
+
 extern "C" {
 
 int ort_host_abi_version(void) { return ORT_HOST_ABI_VERSION; }
@@ -541,23 +553,24 @@ int ort_host_trace_pupil_vjp(const ort_lens* lens, const double* px, const doubl
 }
 
 // RayOperand.rms_spot_size (optimization/operand/ray.py:300-340) on host memory: the mean
-// of x and y over all n points, then sqrt(mean((x - mx)^2 + (y - my)^2)); sums in index
-// order (one thread: the value does not depend on a thread count). stats: n, mean x,
-// mean y, rms, max radius (the ort_rms_spot layout).
+// of x and y over all n points, then sqrt(mean((x - mx)^2 + (y - my)^2)); pairwise sums
+// (halves down to runs of 8 terms, a chain of 8 + log2(n / 8) additions: a running sum's
+// error grows with sqrt(n) and at 65,537 points 20 mm off axis passed the device tree's
+// bound, tests/test_reductions_cpu.py; one thread: no thread count in the value). stats:
+// n, mean x, mean y, rms, max radius (the ort_rms_spot layout; n = 0: count 0, the rest NaN).
 int ort_host_rms_spot(const double* x, const double* y, int64_t n, double* stats, double* rms) {
   if (n < 0 || !stats || !rms || (n > 0 && (!x || !y))) return ORT_ERR_ARG;
-  double sx = 0.0, sy = 0.0;
-  for (int64_t k = 0; k < n; ++k) {
-    sx += x[k];
-    sy += y[k];
-  }
+  const double sx = pairwise_sum(0, n, [&](int64_t k) { return x[k]; });
+  const double sy = pairwise_sum(0, n, [&](int64_t k) { return y[k]; });
   const double mx = sx / (double)n, my = sy / (double)n;
-  double s2 = 0.0, rmax = 0.0;
+  const double s2 = pairwise_sum(0, n, [&](int64_t k) {
+    const double dx = x[k] - mx, dy = y[k] - my;
+    return dx * dx + dy * dy;
+  });
+  double rmax = 0.0;
   for (int64_t k = 0; k < n; ++k) {
     const double dx = x[k] - mx, dy = y[k] - my;
-    const double r2 = dx * dx + dy * dy;
-    s2 += r2;
-    const double r = sqrt(r2);
+    const double r = sqrt(dx * dx + dy * dy);
     if (r > rmax || r != r) rmax = r;
   }
   const double v = sqrt(s2 / (double)n);
@@ -565,7 +578,7 @@ int ort_host_rms_spot(const double* x, const double* y, int64_t n, double* stats
   stats[1] = mx;
   stats[2] = my;
   stats[3] = v;
-  stats[4] = rmax;
+  stats[4] = n > 0 ? rmax : v;  // no point: NaN like the rest (0 / 0), as ort_rms_spot's row
   *rms = v;
   return ORT_OK;
 }

@@ -1,0 +1,655 @@
+"""Shared by tests/test_reductions_cpu.py and tests/test_gpu_reductions.py: seeded synthetic
+inputs at the chunk, tile and row edges of the analysis reductions (ort_spot_stats,
+ort_spot_partials, ort_rms_spot, ort_rms_spot_vjp, ort_rms_finish, ort_wavefront_opd), their
+references in extended precision, the error bounds, and a float64 NumPy restatement of the
+kernels' order of additions (used on the CPU to show that the bounds hold for that order).
+
+Reference precision. np.longdouble when it has a 64-bit significand (nmant >= 63), otherwise
+exact fractions.Fraction arithmetic (square roots to 2^-100); precision() decides, no test
+skips. The references state the documented operation (include/optiland_rt.h; analysis/
+spot_diagram.py:317-357 and :425-437, optimization/operand/ray.py:300-340, wavefront/opd.py:
+143-157, wavefront/wavefront.py:97-143), never the kernels' partition into chunks. Non-finite
+results (a NaN or inf point that counts, an empty pair) are not rounded: they must come out
+as the same NaN / inf, and every quantity the data leaves finite is checked against a bound.
+
+Bounds. u = 2^-53, relative tolerance 0, every bound computed from the test's own arrays and
+only ever compared with the extended-precision reference. k is the longest chain of additions
+one term passes through: per_thread + ceil(rows / 256) + 20, where per_thread is the rays a
+thread adds (spot_per_thread), rows the partial rows the second level reduces (each thread
+strides over them by 256), and 20 the 6 lane steps plus 4 wave additions (the first to 0.0)
+of each of the two block sums.
+
+  count                        exact
+  sum S = sum t_i              k u sum|t_i|
+  centroid S / n               (k + 1) u sum|t_i| / n  (the division adds u)      =: dx, dy
+  second moment S2 = sum |p_i - c|^2 about the exact centroid c of the ref pair
+                               (k + 4) u S2 + 2 (dx sum|x_i - cx| + dy sum|y_i - cy|)
+                               + n (dx^2 + dy^2)
+                               (4 u: the subtraction, the square, the sum of the two squares;
+                               the middle term is the kernel's centroid error, first order in
+                               dx, dy of the REF pair, and vanishes to first order only for
+                               the ref pair itself; the last term is its second order)
+  rms sqrt(S2 / n)             (0.5 |dS2| / S2 + 2 u) rms  (the division and the square root)
+  max radius                   hypot(dx, dy) + 3 u max
+
+ort_spot_partials phase 2 is handed the reduced sums: its centroid is fl(sum / count) of
+float64 inputs taken as exact, so dx = u |cx|, dy = u |cy| there. The two simulated ranks'
+rows combined in rank order have k = max over the ranks + (ranks - 1).
+
+ort_rms_finish. The float64 rows (n_b, sx_b, sy_b, M2_b) handed to the kernel are exact
+inputs; the reference is sum_b [M2_b + n_b |c_b - c|^2] with c_b = s_b / n_b, c = sum s_b /
+sum n_b, all in extended precision; k = ceil(n_rows / 256) + 20 and the terms are the rows'.
+Two constants of the table are too tight for this kernel and are corrected here: (a) a term
+is M2_b + n_b (ddx^2 + ddy^2): subtraction, squares, their sum, the product with n_b and the
+addition to M2_b are 7 roundings, so (k + 7) u replaces (k + 4) u; (b) the kernel rounds every
+row's own centroid s_b / n_b before it subtracts the total centroid, an error of u |c_b| in
+ddx that acts exactly like a centroid error, so dx + u max_b|c_b,x| (dy likewise) replaces
+dx in the middle and last terms, with sum_b n_b |c_b - c| in the place of sum_i |x_i - cx|.
+For the far, tight point set this term is 50 times the (k + 7) u one, so without it the
+bound would call correct arithmetic wrong.
+
+ort_rms_spot_vjp. Elementwise against (x_i - cx) w, w = g / (n rms), formed in extended
+precision from the kernel's own stats row: the subtraction, the product n rms, the division
+and the final product are 4 roundings, |dg_i| <= g4 |g_i| with g4 = 4 u / (1 - 4 u) (the
+first-order 4 u is exceeded by 6 u^2 in the worst case). The |w| d term of a centroid error d
+is zero here because the reference reads the same stats row as the kernel.
+
+ort_wavefront_opd. Per-ray outputs bit for bit against wavefront_terms(), the kernel's
+elementwise chain in float64 NumPy in the same operation order (the kernels are compiled with
+-ffp-contract=off); the 11 sums against the extended-precision sums of those float64 terms
+with the sum bound (per_thread = 1, rows = ceil(n / 256)).
+"""
+
+import functools
+import math
+from fractions import Fraction
+from types import SimpleNamespace
+
+import numpy as np
+
+from optiland_pr_amd import _abi
+from optiland_pr_amd.coordinate_system import CoordinateSystem
+
+U = 2.0 ** -53
+THREADS = 256            # csrc/ort_reduce.h kRedThreads
+SPOT_MAX_CHUNKS = 256    # csrc/ort_k_spot.hip kSpotMaxChunks
+RMS_MAX_CHUNKS = 1024    # csrc/ort_k_spot.hip kRmsMaxChunks
+FINISH_REG_ROWS = 16 * 256  # rows rms_finish_block holds in registers
+
+POINT_SETS = ("centred", "far")
+N_FIELDS, N_WL, REF_WL = 2, 3, 1
+SPOT_SIZES = (0, 1, 63, 64, 65, 255, 256, 257, 65535, 65536, 65537, 131073)
+SPOT_VARIANT_SIZES = (257, 65537)
+SPOT_VARIANTS = ("ref_masked", "nan_tail", "nan_ref", "inf", "local")
+PARTIAL_SIZES = (1, 257, 65537)
+RMS_SIZES = (1, 2, 64, 255, 256, 257, 65537, 262143, 262144, 262145)
+FINISH_ROWS = (1, 2, 255, 256, 257, 4095, 4096, 4097, 4353)
+FINISH_VARIANTS = ("plain", "last_one", "empty_row")
+WAVEFRONT_SIZES = (1, 255, 256, 257, 65537)
+
+
+# -- extended precision ----------------------------------------------------------------
+class _LongDouble:
+    name = "longdouble"
+
+    @staticmethod
+    def arr(a):
+        return np.asarray(a, dtype=np.longdouble)
+
+    @staticmethod
+    def num(v):
+        return np.longdouble(v)
+
+    @staticmethod
+    def sum(a):
+        return np.sum(a, dtype=np.longdouble) if np.size(a) else np.longdouble(0)
+
+    @staticmethod
+    def sqrt(v):
+        return np.sqrt(v)
+
+
+class _Exact:
+    name = "fraction"
+
+    @staticmethod
+    def arr(a):
+        a = np.asarray(a, dtype=np.float64)
+        out = np.empty(a.size, dtype=object)
+        out[:] = [Fraction(float(v)) for v in a.ravel()]
+        return out.reshape(a.shape)
+
+    @staticmethod
+    def num(v):
+        return Fraction(float(v)) if not isinstance(v, Fraction) else v
+
+    @staticmethod
+    def sum(a):
+        return sum(np.asarray(a, dtype=object).ravel().tolist(), Fraction(0))
+
+    @staticmethod
+    def sqrt(v):
+        v = Fraction(v)
+        return Fraction(math.isqrt(v.numerator * (1 << 200) // v.denominator), 1 << 100)
+
+
+def precision():
+    return _LongDouble if np.finfo(np.longdouble).nmant >= 63 else _Exact
+
+
+def _finite(v):
+    return math.isfinite(float(v))
+
+
+def _f64(a):
+    return np.asarray(a).astype(np.float64)
+
+
+WORST = {}  # label -> largest observed error / bound (the tests' report)
+
+
+def check(label, got, ref, bound, X=None):
+    """got (float64) against ref (extended, or a non-finite float) within bound, relative
+    tolerance 0; non-finite references must come out identical. Records error / bound."""
+    X = X or precision()
+    got = float(got)
+    if not _finite(ref):
+        ref = float(ref)
+        assert (math.isnan(got) and math.isnan(ref)) or got == ref, \
+            f"{label}: got {got!r}, expected {ref!r}"
+        return
+    assert math.isfinite(got), f"{label}: got {got!r}, expected {float(ref)!r}"
+    err = float(abs(X.num(got) - ref))
+    ratio = err / bound if bound > 0.0 else (0.0 if err == 0.0 else math.inf)
+    WORST[label] = max(WORST.get(label, 0.0), ratio)
+    assert err <= bound, f"{label}: |{got!r} - {float(ref)!r}| = {err:.3e} > {bound:.3e}"
+
+
+def check_array(label, got, ref, bound, X=None):
+    """Elementwise check() of arrays (bound: array or scalar); NaN / inf exactly where ref's."""
+    X = X or precision()
+    got = np.asarray(got, dtype=np.float64)
+    ref_f = _f64(ref).reshape(got.shape)
+    fin = np.isfinite(ref_f)
+    np.testing.assert_array_equal(got[~fin], ref_f[~fin], err_msg=label)
+    assert np.all(np.isfinite(got[fin])), label
+    if not fin.any():
+        return
+    err = _f64(abs(X.arr(got) - ref)).reshape(got.shape)[fin]
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), got.shape)[fin]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0.0, err / bound, np.where(err == 0.0, 0.0, np.inf))
+    WORST[label] = max(WORST.get(label, 0.0), float(ratio.max()))
+    worst = int(np.argmax(ratio))
+    assert np.all(err <= bound), f"{label}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
+
+
+def report():
+    return "\n".join(f"  {k}: {v:.4f}" for k, v in sorted(WORST.items()))
+
+
+# -- launch shapes (ort_k_spot.hip spot_per_thread / spot_chunks) ------------------------
+def launch_shape(n, max_chunks=SPOT_MAX_CHUNKS):
+    cap = max_chunks * THREADS
+    per_thread = -(-n // cap) if n > cap else 1
+    chunk = per_thread * THREADS
+    return per_thread, (-(-n // chunk) if n > 0 else 1)
+
+
+def chain(n, max_chunks=SPOT_MAX_CHUNKS):
+    """k of a spot / rms launch over n points per pair."""
+    per_thread, rows = launch_shape(n, max_chunks)
+    return per_thread + -(-rows // THREADS) + 20
+
+
+def chain_rows(n_rows):
+    """k of a launch whose threads add one term each (or none) before n_rows rows."""
+    return -(-n_rows // THREADS) + 20
+
+
+# -- synthetic points --------------------------------------------------------------------
+def _points(g, kind, shape):
+    if kind == "centred":
+        return g.normal(0.0, 1.0, shape), g.normal(0.0, 1.0, shape)
+    assert kind == "far"
+    return 20.0 + 1e-3 * g.normal(0.0, 1.0, shape), -35.0 + 1e-3 * g.normal(0.0, 1.0, shape)
+
+
+def _freeze(ns):
+    for v in vars(ns).values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return ns
+
+
+def image_cs():
+    """A tilted, decentred image surface (as tests/test_gpu_spot_stats.py tilts one)."""
+    return CoordinateSystem(x=-0.1, y=0.3, z=0.05, rx=0.05, ry=-0.02, rz=0.01)
+
+
+def cs_records(ops):
+    cs = np.zeros(len(ops), dtype=_abi.CS_OP)
+    for k, (kind, p) in enumerate(ops):
+        cs[k]["kind"] = kind
+        cs[k]["p"] = p
+    return cs
+
+
+@functools.lru_cache(maxsize=None)
+def spot_problem(kind, n_pupil, variant="plain"):
+    """2 fields x 3 wavelengths of n_pupil points, ref_wl = 1. About 10% of i drawn from
+    {0, -0.0, -1, NaN} (a tenth of those points with NaN coordinates, as a clipped ray has).
+    x, y, z, i: [6][n_pupil]; xl, yl: the points in the image frame (the oracle's apply_cs
+    for variant "local", x and y themselves otherwise)."""
+    pairs = N_FIELDS * N_WL
+    g = np.random.default_rng(7919 * n_pupil + 31 * POINT_SETS.index(kind)
+                              + (1 + SPOT_VARIANTS.index(variant) if variant != "plain" else 0))
+    x, y = _points(g, kind, (pairs, n_pupil))
+    z = g.normal(0.0, 0.01, (pairs, n_pupil))
+    i = g.uniform(0.2, 1.0, (pairs, n_pupil))
+    off = g.random((pairs, n_pupil)) < 0.1
+    i[off] = g.choice(np.array([0.0, -0.0, -1.0, np.nan]), int(off.sum()))
+    lost = off & (g.random((pairs, n_pupil)) < 0.1)
+    x0, y0 = x.copy(), y.copy()
+    x[lost] = np.nan
+    y[lost] = np.nan
+    ops = None
+    if n_pupil:
+        if variant == "ref_masked":      # field 0's ref pair: no point counts
+            i[REF_WL] = g.choice(np.array([0.0, -0.0, -1.0, np.nan]), n_pupil)
+        elif variant == "nan_tail":      # last point of the last chunk of a non-ref pair
+            x[2, -1], y[2, -1], i[2, -1] = np.nan, y0[2, -1], 1.0
+        elif variant == "nan_ref":       # one NaN point in field 0's ref pair
+            j = n_pupil // 2
+            x[REF_WL, j], y[REF_WL, j], i[REF_WL, j] = x0[REF_WL, j], np.nan, 1.0
+        elif variant == "inf":           # one +inf point in field 1's ref pair
+            j, p = n_pupil // 3, N_WL + REF_WL
+            x[p, j], y[p, j], i[p, j] = x0[p, j], np.inf, 0.5
+    xl, yl = x, y
+    if variant == "local":
+        from oracle import trace_np
+
+        ops = cs_records(image_cs().localize_ops())
+        zero = np.zeros(x.size)
+        r = trace_np.Rays(x.ravel(), y.ravel(), z.ravel(), zero, zero, zero, zero)
+        with np.errstate(invalid="ignore"):
+            trace_np.apply_cs(r, ops)
+        xl, yl = r.x.reshape(x.shape), r.y.reshape(y.shape)
+    return _freeze(SimpleNamespace(kind=kind, n=n_pupil, variant=variant, x=x, y=y, z=z, i=i,
+                                   xl=xl, yl=yl, ops=ops))
+
+
+@functools.lru_cache(maxsize=None)
+def rms_problem(kind, n, nan=False):
+    g = np.random.default_rng(104729 * n + POINT_SETS.index(kind))
+    x, y = _points(g, kind, n)
+    if nan and n:
+        x[n - 1 - n // 3] = np.nan
+    return _freeze(SimpleNamespace(kind=kind, n=n, x=x, y=y))
+
+
+@functools.lru_cache(maxsize=None)
+def finish_problem(kind, n_rows, variant="plain"):
+    """The F_RMS rows (n_b, sum x, sum y, M2_b about the block's own float64 centroid) of
+    per-256-point blocks, formed on the host in float64; the last block is partial (one point
+    for "last_one": M2_b = 0), "empty_row" zeroes one interior row (n_b = 0) and drops its
+    points. -> rows [n_rows][4] and the underlying points x, y."""
+    g = np.random.default_rng(15485863 * n_rows + POINT_SETS.index(kind)
+                              + 7 * FINISH_VARIANTS.index(variant))
+    last = 1 if variant == "last_one" else 1 + (n_rows * 37) % 255
+    sizes = np.full(n_rows, THREADS)
+    sizes[-1] = last
+    if variant == "empty_row" and n_rows > 2:
+        sizes[n_rows // 2] = 0
+    x, y = _points(g, kind, int(sizes.sum()))
+    rows = np.zeros((n_rows, 4))
+    start = 0
+    for b, nb in enumerate(sizes):
+        if nb:
+            xb, yb = x[start:start + nb], y[start:start + nb]
+            sx, sy = float(np.sum(xb)), float(np.sum(yb))
+            dx, dy = xb - sx / nb, yb - sy / nb
+            rows[b] = nb, sx, sy, float(np.sum(dx * dx + dy * dy))
+        start += nb
+    return _freeze(SimpleNamespace(kind=kind, n_rows=n_rows, variant=variant, rows=rows,
+                                   x=x, y=y))
+
+
+# -- references in extended precision -----------------------------------------------------
+def _sum_or_pattern(X, a):
+    """(sum, sum |.|) of float64 a: extended when every entry is finite, else the float64
+    sum, whose NaN / inf is exact."""
+    if np.all(np.isfinite(a)):
+        e = X.arr(a)
+        return X.sum(e), float(X.sum(abs(e)))
+    with np.errstate(invalid="ignore"):
+        return float(np.sum(a)), math.nan
+
+
+def spot_reference(x, y, i, n_fields, n_wl, ref_wl, k, gsum=None, X=None):
+    """Per pair of x, y [pairs][n] (image frame), mask i > 0 (None: every point counts):
+    count n; sums sx, sy and centroid cx, cy of the pair's own points; s2, rms, geo (max
+    radius) and the partial rows' max m / NaN flag about the ref pair's centroid (about
+    gsum[ref][1:3] / gsum[ref][0], float64 rows taken as exact, when gsum is given); every
+    value with its bound b_* as the module docstring states them."""
+    X = X or precision()
+    pairs = n_fields * n_wl
+    own = []
+    for p in range(pairs):
+        on = np.ones(x.shape[1], dtype=bool) if i is None else i[p] > 0
+        xs, ys = x[p][on], y[p][on]
+        n = int(on.sum())
+        sx, ax = _sum_or_pattern(X, xs)
+        sy, ay = _sum_or_pattern(X, ys)
+        r = SimpleNamespace(n=n, xs=xs, ys=ys, sx=sx, sy=sy, b_sx=k * U * ax, b_sy=k * U * ay)
+        if n == 0:
+            r.cx = r.cy = math.nan
+            r.b_cx = r.b_cy = math.nan
+        else:
+            r.cx = sx / n if _finite(sx) else float(sx) / n
+            r.cy = sy / n if _finite(sy) else float(sy) / n
+            r.b_cx, r.b_cy = (k + 1) * U * ax / n, (k + 1) * U * ay / n
+        own.append(r)
+    for p, r in enumerate(own):
+        ref = (p // n_wl) * n_wl + ref_wl
+        if gsum is not None:
+            c0, c1, c2 = (float(v) for v in gsum[ref])
+            ok = c0 != 0.0 and all(math.isfinite(v) for v in (c0, c1, c2))
+            if ok:
+                cx, cy = X.num(c1) / X.num(c0), X.num(c2) / X.num(c0)
+                ddx, ddy = U * abs(float(cx)), U * abs(float(cy))
+            else:
+                with np.errstate(all="ignore"):
+                    cx = float(np.float64(c1) / np.float64(c0))
+                    cy = float(np.float64(c2) / np.float64(c0))
+                ddx = ddy = math.nan
+        else:
+            cx, cy, ddx, ddy = own[ref].cx, own[ref].cy, own[ref].b_cx, own[ref].b_cy
+        data_ok = np.all(np.isfinite(r.xs)) and np.all(np.isfinite(r.ys))
+        if data_ok and _finite(cx) and _finite(cy):
+            ex, ey = X.arr(r.xs) - cx, X.arr(r.ys) - cy
+            r2 = ex * ex + ey * ey
+            r.s2 = X.sum(r2)
+            s2 = float(r.s2)
+            r.b_s2 = ((k + 4) * U * s2
+                      + 2.0 * (ddx * float(X.sum(abs(ex))) + ddy * float(X.sum(abs(ey))))
+                      + r.n * (ddx * ddx + ddy * ddy))
+            r.m = X.sqrt(r2.max()) if r.n else X.num(0.0)
+            r.b_m = math.hypot(ddx, ddy) + 3.0 * U * float(r.m)
+            r.flag = 0.0
+            if r.n:
+                r.rms = X.sqrt(r.s2 / r.n)
+                r.b_rms = (0.5 * r.b_s2 / s2 + 2.0 * U) * float(r.rms) if s2 > 0.0 else \
+                    math.sqrt(r.b_s2 / r.n)
+                r.geo, r.b_geo = r.m, r.b_m
+            else:
+                r.rms = r.geo = math.nan
+                r.b_rms = r.b_geo = math.nan
+        else:  # the non-finite pattern, exact in float64 (spot_diagram.py:317-357 in NumPy)
+            with np.errstate(all="ignore"):
+                ex, ey = r.xs - float(cx), r.ys - float(cy)
+                r2 = ex * ex + ey * ey
+                r.s2 = float(np.sum(r2))
+                rad = np.sqrt(r2)
+                r.flag = 1.0 if np.isnan(rad).any() else 0.0
+                r.m, r.b_m = float(np.max(rad[~np.isnan(rad)], initial=0.0)), 0.0
+                if 0.0 < r.m < math.inf:  # finite radii beside a NaN one: their max, bounded
+                    keep = np.isfinite(rad)
+                    ex, ey = X.arr(r.xs[keep]) - cx, X.arr(r.ys[keep]) - cy
+                    r.m = X.sqrt((ex * ex + ey * ey).max())
+                    r.b_m = math.hypot(ddx, ddy) + 3.0 * U * float(r.m)
+                r.rms = float(np.sqrt(r.s2 / r.n)) if r.n else math.nan
+                r.geo = float(np.max(rad)) if r.n else math.nan
+            assert not math.isfinite(r.s2) or r.n == 0
+            r.b_rms = r.b_geo = math.nan
+            r.b_s2 = 0.0  # no point: 0 exactly (else non-finite)
+    return own
+
+
+def check_spot_rows(label, got, ref):
+    """ort_spot_stats / ort_rms_spot rows [pairs][5] against spot_reference()."""
+    for p, r in enumerate(ref):
+        assert got[p, 0] == r.n, f"{label} pair {p}: count {got[p, 0]} != {r.n}"
+        check(f"{label} centroid", got[p, 1], r.cx, r.b_cx)
+        check(f"{label} centroid", got[p, 2], r.cy, r.b_cy)
+        check(f"{label} rms", got[p, 3], r.rms, r.b_rms)
+        check(f"{label} max radius", got[p, 4], r.geo, r.b_geo)
+
+
+def check_partial_rows(label, phase, got, ref):
+    """ort_spot_partials rows [pairs][3] of one phase against spot_reference()."""
+    for p, r in enumerate(ref):
+        if phase == 1:
+            assert got[p, 0] == r.n, f"{label} pair {p}: count {got[p, 0]} != {r.n}"
+            check(f"{label} sum", got[p, 1], r.sx, r.b_sx)
+            check(f"{label} sum", got[p, 2], r.sy, r.b_sy)
+        else:
+            check(f"{label} sum r^2", got[p, 0], r.s2, r.b_s2)
+            # a NaN radius leaves the max (the flag carries it): the max of the rest
+            check(f"{label} max radius", got[p, 1], r.m, r.b_m)
+            assert got[p, 2] == r.flag, f"{label} pair {p}: flag {got[p, 2]} != {r.flag}"
+
+
+def finish_reference(rows, X=None):
+    """ort_rms_finish of float64 rows taken as exact -> n, cx, cy, rms with bounds."""
+    X = X or precision()
+    k = chain_rows(rows.shape[0])
+    nb = X.arr(rows[:, 0])
+    n = X.sum(nb)
+    r = SimpleNamespace(n=float(n))
+    r.cx, r.cy = X.sum(X.arr(rows[:, 1])) / n, X.sum(X.arr(rows[:, 2])) / n
+    r.b_cx = (k + 1) * U * float(np.sum(np.abs(rows[:, 1]))) / r.n
+    r.b_cy = (k + 1) * U * float(np.sum(np.abs(rows[:, 2]))) / r.n
+    live = rows[:, 0] > 0
+    nl = X.arr(rows[live, 0])
+    ex = X.arr(rows[live, 1]) / nl - r.cx
+    ey = X.arr(rows[live, 2]) / nl - r.cy
+    r.s2 = X.sum(X.arr(rows[live, 3]) + nl * (ex * ex + ey * ey))
+    s2 = float(r.s2)
+    ddx = r.b_cx + U * float(np.max(np.abs(rows[live, 1] / rows[live, 0])))
+    ddy = r.b_cy + U * float(np.max(np.abs(rows[live, 2] / rows[live, 0])))
+    r.b_s2 = ((k + 7) * U * s2
+              + 2.0 * (ddx * float(X.sum(nl * abs(ex))) + ddy * float(X.sum(nl * abs(ey))))
+              + r.n * (ddx * ddx + ddy * ddy))
+    r.rms = X.sqrt(r.s2 / n)
+    r.b_rms = (0.5 * r.b_s2 / s2 + 2.0 * U) * float(r.rms) if s2 > 0.0 else \
+        math.sqrt(r.b_s2 / r.n)
+    return r
+
+
+def check_finish(label, stats, ref):
+    assert stats[0] == ref.n, f"{label}: count {stats[0]} != {ref.n}"
+    check(f"{label} centroid", stats[1], ref.cx, ref.b_cx)
+    check(f"{label} centroid", stats[2], ref.cy, ref.b_cy)
+    check(f"{label} rms", stats[3], ref.rms, ref.b_rms)
+    assert math.isnan(stats[4]), f"{label}: stats[4] = {stats[4]}"
+
+
+def vjp_reference(x, y, stats, g, X=None):
+    """(gx, gy, bound x, bound y) of ort_rms_spot_vjp from the kernel's own stats row."""
+    X = X or precision()
+    g4 = 4.0 * U / (1.0 - 4.0 * U)
+    n, cx, cy, rms = (float(v) for v in stats[:4])
+    if not (rms > 0.0 and math.isfinite(rms) and math.isfinite(cx) and math.isfinite(cy)
+            and np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        with np.errstate(all="ignore"):  # the NaN / inf pattern, exact in float64
+            w = np.float64(g) / (np.float64(n) * np.float64(rms))
+            gx, gy = (x - cx) * w, (y - cy) * w
+        assert not np.isfinite(gx).any() and not np.isfinite(gy).any()
+        return gx, gy, np.zeros_like(gx), np.zeros_like(gy)
+    w = X.num(g) / (X.num(n) * X.num(rms))
+    gx, gy = (X.arr(x) - X.num(cx)) * w, (X.arr(y) - X.num(cy)) * w
+    return gx, gy, g4 * _f64(abs(gx)), g4 * _f64(abs(gy))
+
+
+# -- the wavefront ---------------------------------------------------------------------
+WF_FIELDS = ("xc", "yc", "zc", "xc2", "yc2", "zc2", "r2", "n_image", "opd_ref", "ux", "uy", "epd",
+             "wl_mm")
+
+
+@functools.lru_cache(maxsize=None)
+def wavefront_problem(n, nan=False):
+    """n image-plane rays about a reference sphere of radius 100 mm centred near the image
+    point. Most start inside it (near root negative: the t < 0 branch takes the far root);
+    about 6% start 150 mm behind it (both roots positive), about 6% pass beside it (d < 0,
+    clamped), 10% have i in {0, -1} (and NaN when `nan`, which also makes one ray NaN)."""
+    g = np.random.default_rng(86028121 + 2 * n + int(nan))
+    ref = {"xc": 0.1, "yc": -0.2, "zc": 0.03, "r2": 100.0 ** 2, "n_image": 1.0003,
+           "opd_ref": 151.25, "ux": 0.0123, "uy": -0.0456, "epd": 12.5, "wl_mm": 0.55e-3}
+    for a in "xyz":
+        ref[a + "c2"] = float(np.float64(ref[a + "c"]) ** 2)
+    r = {a: g.normal(0.0, 0.05, n) for a in "xyz"}
+    L, M = g.normal(0.0, 0.05, n), g.normal(0.0, 0.05, n)
+    r["L"], r["M"], r["N"] = L, M, np.sqrt(1.0 - L * L - M * M)
+    pick = g.random(n)
+    r["z"] = np.where(pick < 0.06, 150.0 + r["z"], r["z"])
+    r["x"] = np.where((pick >= 0.06) & (pick < 0.12), 200.0 + r["x"], r["x"])
+    r["opd"] = 150.0 + g.normal(0.0, 1e-3, n)
+    i = g.uniform(0.2, 1.0, n)
+    off = g.random(n) < 0.1
+    i[off] = g.choice(np.array([0.0, -1.0, np.nan] if nan else [0.0, -1.0]), int(off.sum()))
+    r["i"] = i
+    if nan and n:
+        r["y"][n // 2], r["i"][n // 2] = np.nan, 1.0
+    px, py = g.uniform(-1.0, 1.0, n), g.uniform(-1.0, 1.0, n)
+    for a in (*r.values(), px, py):
+        a.setflags(write=False)
+    return SimpleNamespace(n=n, rays=r, px=px, py=py, ref=ref)
+
+
+def wavefront_terms(rays, px, py, q, tilt):
+    """wavefront_opd_kernel's elementwise chain in float64 NumPy, operation for operation
+    (strategy.py:94-116, :150-166, :226-230; opd.py:151-157; wavefront.py:116-131) ->
+    (opd_wv, pupil_x, pupil_y, pupil_z, terms [11][n])."""
+    xr, yr, zr = rays["x"], rays["y"], rays["z"]
+    with np.errstate(all="ignore"):
+        L, M, N = -rays["L"], -rays["M"], -rays["N"]
+        aa = L * L + M * M + N * N
+        b = 2.0 * (L * (xr - q["xc"]) + M * (yr - q["yc"]) + N * (zr - q["zc"]))
+        c = (xr * xr + yr * yr + zr * zr - 2.0 * (xr * q["xc"] + yr * q["yc"] + zr * q["zc"])
+             + q["xc2"] + q["yc2"] + q["zc2"] - q["r2"])
+        d = b * b - 4.0 * aa * c
+        d = np.where(d < 0.0, 0.0, d)
+        t = (-b - np.sqrt(d)) / (2.0 * aa)
+        t = np.where(t < 0.0, (-b + np.sqrt(d)) / (2.0 * aa), t)
+        opd_img = q["n_image"] * t
+        opd = rays["opd"] - opd_img
+        if tilt:
+            X = px * q["epd"] / 2.0
+            Y = py * q["epd"] / 2.0
+            opd = opd + (q["ux"] * X + q["uy"] * Y)
+        wv = (q["opd_ref"] - opd) / q["wl_mm"]
+        tp = opd_img / q["n_image"]
+        xp = xr - tp * rays["L"]
+        yp = yr - tp * rays["M"]
+        zp = zr - tp * rays["N"]
+        w = rays["i"]
+        on = w > 0.0
+        terms = np.stack([np.where(on, 1.0, 0.0), np.where(on, wv * wv, 0.0), w, w * xp, w * yp,
+                          w * xp * xp, w * xp * yp, w * yp * yp, w * wv, w * xp * wv,
+                          w * yp * wv])
+    return wv, xp, yp, zp, terms
+
+
+def wavefront_reference(terms, X=None):
+    """The 11 sums of the float64 terms in extended precision with the sum bound."""
+    X = X or precision()
+    k = chain_rows(max(1, -(-terms.shape[1] // THREADS)))
+    out = [_sum_or_pattern(X, t) for t in terms]
+    return [s for s, _ in out], [k * U * a for _, a in out]
+
+
+# -- the kernels' order of additions, in float64 NumPy -----------------------------------
+def tree64(v):
+    """wave_sum: adjacent lanes pairwise, six times (the DPP steps' tree)."""
+    for _ in range(6):
+        v = v[..., 0::2] + v[..., 1::2]
+    return v[..., 0]
+
+
+def block_sum(v):
+    """block_sum over [..., 256]: the four waves' sums added in order to 0.0."""
+    w = tree64(v.reshape(v.shape[:-1] + (THREADS // 64, 64)))
+    s = np.zeros(w.shape[:-1])
+    for k in range(THREADS // 64):
+        s = s + w[..., k]
+    return s
+
+
+def rows_sum(rows):
+    """reduce_rows / reduce_rows_n over [..., n]: thread t adds rows t, t + 256, ... in
+    index order, then block_sum."""
+    n = rows.shape[-1]
+    steps = max(1, -(-n // THREADS))
+    pad = np.zeros(rows.shape[:-1] + (steps * THREADS,))
+    pad[..., :n] = rows
+    pad = pad.reshape(rows.shape[:-1] + (steps, THREADS))
+    v = np.zeros(rows.shape[:-1] + (THREADS,))
+    for c in range(steps):
+        v = v + pad[..., c, :]
+    return block_sum(v)
+
+
+def chunk_sums(vals, on, max_chunks):
+    """chunk_points + block_sum: the partial row of every chunk of [..., n] values, thread t
+    of a chunk adding its rays t, t + 256, ... (k < per_thread) where `on`."""
+    n = vals.shape[-1]
+    per_thread, chunks = launch_shape(n, max_chunks)
+    shape = vals.shape[:-1] + (chunks * per_thread * THREADS,)
+    pv, po = np.zeros(shape), np.zeros(shape, dtype=bool)
+    pv[..., :n], po[..., :n] = vals, on
+    split = vals.shape[:-1] + (chunks, per_thread, THREADS)
+    pv, po = pv.reshape(split), po.reshape(split)
+    v = np.zeros(vals.shape[:-1] + (chunks, THREADS))
+    with np.errstate(invalid="ignore"):
+        for k in range(per_thread):
+            v = np.where(po[..., k, :], v + pv[..., k, :], v)
+    return block_sum(v)
+
+
+def kernel_spot(x, y, i, n_wl, ref_wl, max_chunks=SPOT_MAX_CHUNKS, gsum=None):
+    """spot_sum_kernel, spot_dev_kernel and spot_final_kernel / spot_pair_kernel in their
+    order -> (out [pairs][5], phase-1 rows [pairs][3], phase-2 rows [pairs][3])."""
+    pairs = x.shape[0]
+    on = np.ones(x.shape, dtype=bool) if i is None else i > 0
+    with np.errstate(all="ignore"):
+        own = np.stack([rows_sum(chunk_sums(v, on, max_chunks))
+                        for v in (np.ones(x.shape), x, y)], axis=1)
+        ref = (np.arange(pairs) // n_wl) * n_wl + ref_wl
+        c = own[ref] if gsum is None else np.asarray(gsum)[ref]
+        cx, cy = c[:, 1] / c[:, 0], c[:, 2] / c[:, 0]
+        dx, dy = x - cx[:, None], y - cy[:, None]
+        r2 = dx * dx + dy * dy
+        t = rows_sum(chunk_sums(r2, on, max_chunks))
+        rad = np.sqrt(r2)
+        flag = np.any(on & np.isnan(rad), axis=1).astype(np.float64)
+        m = np.max(np.where(on & ~np.isnan(rad), rad, 0.0), axis=1, initial=0.0)
+        n = own[:, 0]
+        out = np.stack([n, own[:, 1] / n, own[:, 2] / n, np.sqrt(t / n),
+                        np.where((flag != 0) | np.isnan(t) | (n == 0), np.nan, m)], axis=1)
+    return out, own, np.stack([t, m, flag], axis=1)
+
+
+def kernel_finish(rows):
+    """rms_finish_block: rows strided by 256 (the first 16 per thread from registers, the
+    rest re-read: one order), block_sum; then the rows' Chan terms the same way."""
+    with np.errstate(all="ignore"):
+        v = [rows_sum(rows[:, f]) for f in range(3)]
+        mx, my = v[1] / v[0], v[2] / v[0]
+        nb = rows[:, 0]
+        live = nb > 0.0
+        safe = np.where(live, nb, 1.0)
+        dx, dy = rows[:, 1] / safe - mx, rows[:, 2] / safe - my
+        term = np.where(live, rows[:, 3] + nb * (dx * dx + dy * dy), 0.0)
+        m = rows_sum(term)
+        return np.array([v[0], mx, my, np.sqrt(m / v[0]), np.nan])
+
+
+def kernel_wavefront_sums(terms):
+    """wavefront_opd_kernel's block sums and wavefront_final_kernel's reduce_rows_n."""
+    n = terms.shape[1]
+    blocks = max(1, -(-n // THREADS))
+    pad = np.zeros((terms.shape[0], blocks * THREADS))
+    pad[:, :n] = terms
+    with np.errstate(invalid="ignore"):
+        return rows_sum(block_sum(pad.reshape(terms.shape[0], blocks, THREADS)))
