@@ -607,21 +607,93 @@ __device__ inline int newton_decide(const ort_surface* surf, int32_t n_surf, int
 }
 
 
-__device__ inline void store_ray(const KArgs& a, int64_t rid, const ort::Ray& r) {
+// The pieces the Newton kernel (trace_ray, trace_block) and the closed-form kernel
+// (closed_ray_in, closed_surfaces, trace_closed_kernel) share. Each issues its operations
+// in the order the kernels had them spelled out, so the kernels' code is unchanged: the
+// ray is filled and the intensity (whose exp is a branch) evaluated in place, between the
+// N and the opd store.
+// the caller's ray r_ld (kernels without F_GEN)
+__device__ inline void load_ray(const KArgs& a, int64_t r_ld, ort::Ray& r) {
+  r.x = a.in.x[r_ld];
+  r.y = a.in.y[r_ld];
+  r.z = a.in.z[r_ld];
+  r.L = a.in.L[r_ld];
+  r.M = a.in.M[r_ld];
+  r.N = a.in.N[r_ld];
+  r.i = a.in.i[r_ld];
+  r.opd = a.in.opd[r_ld];
+  r.att = 0.0;
+}
+
+// inten: the intensity to store instead of the ray's own (trace_closed_kernel's apodized one)
+__device__ inline void store_ray(const KArgs& a, int64_t rid, const ort::Ray& r,
+                                 const double* inten = nullptr) {
   ORT_ST(a.out.x[rid], r.x);
   ORT_ST(a.out.y[rid], r.y);
   ORT_ST(a.out.z[rid], r.z);
   ORT_ST(a.out.L[rid], r.L);
   ORT_ST(a.out.M[rid], r.M);
   ORT_ST(a.out.N[rid], r.N);
-  ORT_ST(a.out.i[rid], ort::intensity(r));
+  ORT_ST(a.out.i[rid], inten ? *inten : ort::intensity(r));
   ORT_ST(a.out.opd[rid], r.opd);
 }
+
+// F_REC: ray rid's row of a recording surface (after globalize). apod: the pupil factor
+// the closed kernel multiplies into a recorded intensity (closed_surfaces)
+__device__ inline void store_record(const KArgs& a, const ort_surface& s, int64_t rid,
+                                    const ort::Ray& r, const double* apod = nullptr) {
+  double* base = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + rid;
+  ORT_ST(base[0 * a.n_rays], r.x);
+  ORT_ST(base[1 * a.n_rays], r.y);
+  ORT_ST(base[2 * a.n_rays], r.z);
+  ORT_ST(base[3 * a.n_rays], r.L);
+  ORT_ST(base[4 * a.n_rays], r.M);
+  ORT_ST(base[5 * a.n_rays], r.N);
+  ORT_ST(base[6 * a.n_rays], apod ? *apod * ort::intensity(r) : ort::intensity(r));
+  ORT_ST(base[7 * a.n_rays], r.opd);
+}
+
+// F_TAPE: the ray as it arrives at a surface (global frame), rows 0..5 of the surface's
+// tape rows tp of this ray
+__device__ inline void store_tape_point(const KArgs& a, double* tp, const ort::Ray& r) {
+  ORT_ST(tp[0], r.x);
+  ORT_ST(tp[a.n_rays], r.y);
+  ORT_ST(tp[2 * a.n_rays], r.z);
+  ORT_ST(tp[3 * a.n_rays], r.L);
+  ORT_ST(tp[4 * a.n_rays], r.M);
+  ORT_ST(tp[5 * a.n_rays], r.N);
+}
+
+// The ray moved to its intersection at distance t: propagate, OPD, aperture clips
+// (standard_surface.py:215-223). AP_PROG = false: without the aperture program (the
+// ORT_NO_AP_PROG A/B builds of the closed-form step)
+template <bool AP_PROG = true>
+__device__ inline void to_intersection(const KArgs& a, const ort_surface& s, ort::Ray& r,
+                                       double t, double alpha, double n_pre) {
+  ort::propagate(r, t, alpha);
+  ort::add_opd(r, t, n_pre);
+  if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
+  if constexpr (AP_PROG) {
+    if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
+  }
+}
+#ifndef ORT_NO_AP_PROG
+constexpr bool kApProg = true;
+#else
+constexpr bool kApProg = false;
+#endif
 
 // One ray through every surface (and the image-space propagate) for trace_kernel.
 // FAST: ort_fastpath.h's sequences with their range failures ORed into `bad` (see
 // kNewtonFast); the lane's records, tape rows and Newton statistics are written only while
 // it is active (the exact pass rewrites a bad lane's).
+// Only FAST = true is instantiated: trace_block carries the exact pass as a second,
+// operation-for-operation copy of this loop. Every form of one shared loop tried so far
+// (trace_block calling trace_ray<FEAT, false>; the ray load split off and the ray passed by
+// reference; the intensity evaluated in place; radius_inf un-hoisted) compiles to other
+// code than the copy -- the taped Zernike forward gains 12-20 B of scratch, the record
+// kernels cross 128 VGPRs (profiles/README.md) -- so a change to a surface step is still
+// made in both. The pieces above are shared.
 template <uint32_t FEAT, bool FAST>
 __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs& a, int64_t rid, bool active, int64_t group,
                                      bool group_uniform, const int32_t* sched, int& range_bits,
@@ -646,15 +718,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
   } else {
     if (a.seg) lam = a.seg[sidx].lambda_idx;
     if constexpr ((FEAT & F_WRAY) != 0) wl = a.w[r_ld];
-    r.x = a.in.x[r_ld];
-    r.y = a.in.y[r_ld];
-    r.z = a.in.z[r_ld];
-    r.L = a.in.L[r_ld];
-    r.M = a.in.M[r_ld];
-    r.N = a.in.N[r_ld];
-    r.i = a.in.i[r_ld];
-    r.opd = a.in.opd[r_ld];
-    r.att = 0.0;
+    load_ray(a, r_ld, r);
     // the fast flat-surface refraction assumes finite directions (ort_fastpath.h)
     if constexpr (FAST) ORT_CHK(bad, !(::fabs(r.L) < __builtin_inf() && ::fabs(r.M) < __builtin_inf()));
   }
@@ -664,28 +728,13 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
       range_bits |= ORT_STATUS_BAD_APODIZATION;
   }
 
-#ifdef ORT_PREFETCH_SURF  // (A/B builds) surface si + 1's record loaded during surface si
-  ort_surface s_next = cst(a.surf)[a.start_surface < a.n_surf ? a.start_surface : 0];
-#endif
   for (int si = a.start_surface; si < a.n_surf; ++si) {
-#ifdef ORT_PREFETCH_SURF
-    const ort_surface s = s_next;
-    s_next = cst(a.surf)[si + 1 < a.n_surf ? si + 1 : si];
-#else
     const ort_surface s = cst(a.surf)[si];
-#endif
     const ort_surface_optics o = surface_optics<FEAT>(a, s, lam, si, wl);
     double* tp = nullptr;  // F_TAPE: this surface's tape rows of this ray
     if constexpr ((FEAT & F_TAPE) != 0) {
       tp = a.tape + tape_row0(a.surf, si) * a.n_rays + rid;
-      if (active) {
-        ORT_ST(tp[0], r.x);
-        ORT_ST(tp[a.n_rays], r.y);
-        ORT_ST(tp[2 * a.n_rays], r.z);
-        ORT_ST(tp[3 * a.n_rays], r.L);
-        ORT_ST(tp[4 * a.n_rays], r.M);
-        ORT_ST(tp[5 * a.n_rays], r.N);
-      }
+      if (active) store_tape_point(a, tp, r);
     }
     localize(a, s, r);
     double t;
@@ -728,10 +777,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
     } else if constexpr (FAST) {
       // the closed kernel's fast surface step (closed_surfaces), the Newton surfaces with
       // the normal of their last evaluation
-      ort::propagate(r, t, alpha);
-      ort::add_opd(r, t, n_pre);
-      if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-      if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
+      to_intersection(a, s, r, t, alpha, n_pre);
       const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
       const bool is_plane = s.geometry == ORT_GEOM_PLANE;
       if (!hn && !refl && (is_plane || (radius_inf && s.geometry == ORT_GEOM_STANDARD))) {
@@ -754,10 +800,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
       }
     } else if constexpr ((FEAT & F_KM) != 0) {
       if (hn) {  // finish_surface with the normal of the last Newton evaluation
-        ort::propagate(r, t, alpha);
-        ort::add_opd(r, t, n_pre);
-        if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-        if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
+        to_intersection(a, s, r, t, alpha, n_pre);
         if (s.flags & ORT_SURF_REFLECTIVE)
           ort::reflect(r, hnx, hny, hnz);
         else
@@ -768,12 +811,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
       }
     } else {
       // closed-form geometries only: plane / conic normal inline
-      ort::propagate(r, t, alpha);
-      ort::add_opd(r, t, n_pre);
-      if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-#ifndef ORT_NO_AP_PROG
-      if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-#endif
+      to_intersection<kApProg>(a, s, r, t, alpha, n_pre);
       double nx, ny, nz;
       if (s.geometry == ORT_GEOM_PLANE) {
         nx = 0.0; ny = 0.0; nz = 1.0;
@@ -789,17 +827,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
     }
     globalize(a, s, r);
     if constexpr ((FEAT & F_REC) != 0) {
-      if ((s.flags & ORT_SURF_RECORD) && active) {
-        double* base = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + rid;
-        ORT_ST(base[0 * a.n_rays], r.x);
-        ORT_ST(base[1 * a.n_rays], r.y);
-        ORT_ST(base[2 * a.n_rays], r.z);
-        ORT_ST(base[3 * a.n_rays], r.L);
-        ORT_ST(base[4 * a.n_rays], r.M);
-        ORT_ST(base[5 * a.n_rays], r.N);
-        ORT_ST(base[6 * a.n_rays], ort::intensity(r));
-        ORT_ST(base[7 * a.n_rays], r.opd);
-      }
+      if ((s.flags & ORT_SURF_RECORD) && active) store_record(a, s, rid, r);
     }
   }
   // real_ray_tracer.py:84-89: image-space propagate by the last surface's thickness
@@ -868,15 +896,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
   } else {
     if (a.seg) lam = a.seg[sidx].lambda_idx;
     if constexpr ((FEAT & F_WRAY) != 0) wl = a.w[r_ld];
-    r.x = a.in.x[r_ld];
-    r.y = a.in.y[r_ld];
-    r.z = a.in.z[r_ld];
-    r.L = a.in.L[r_ld];
-    r.M = a.in.M[r_ld];
-    r.N = a.in.N[r_ld];
-    r.i = a.in.i[r_ld];
-    r.opd = a.in.opd[r_ld];
-    r.att = 0.0;
+    load_ray(a, r_ld, r);
   }
   int64_t group = 0;
   bool group_uniform = true;
@@ -896,28 +916,13 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       range_bits |= ORT_STATUS_BAD_APODIZATION;
   }
 
-#ifdef ORT_PREFETCH_SURF  // (A/B builds) surface si + 1's record loaded during surface si
-  ort_surface s_next = cst(a.surf)[a.start_surface < a.n_surf ? a.start_surface : 0];
-#endif
   for (int si = a.start_surface; si < a.n_surf; ++si) {
-#ifdef ORT_PREFETCH_SURF
-    const ort_surface s = s_next;
-    s_next = cst(a.surf)[si + 1 < a.n_surf ? si + 1 : si];
-#else
     const ort_surface s = cst(a.surf)[si];
-#endif
     const ort_surface_optics o = surface_optics<FEAT>(a, s, lam, si, wl);
     double* tp = nullptr;  // F_TAPE: this surface's tape rows of this ray
     if constexpr ((FEAT & F_TAPE) != 0) {
       tp = a.tape + tape_row0(a.surf, si) * a.n_rays + rid;
-      if (active) {
-        ORT_ST(tp[0], r.x);
-        ORT_ST(tp[a.n_rays], r.y);
-        ORT_ST(tp[2 * a.n_rays], r.z);
-        ORT_ST(tp[3 * a.n_rays], r.L);
-        ORT_ST(tp[4 * a.n_rays], r.M);
-        ORT_ST(tp[5 * a.n_rays], r.N);
-      }
+      if (active) store_tape_point(a, tp, r);
     }
     localize(a, s, r);
     double t;
@@ -953,10 +958,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       interact<FEAT>(a, s, r, o, lam, wl, unnorm);
     } else if constexpr ((FEAT & F_KM) != 0) {
       if (hn) {  // finish_surface with the normal of the last Newton evaluation
-        ort::propagate(r, t, alpha);
-        ort::add_opd(r, t, n_pre);
-        if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-        if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
+        to_intersection(a, s, r, t, alpha, n_pre);
         if (s.flags & ORT_SURF_REFLECTIVE)
           ort::reflect(r, hnx, hny, hnz);
         else
@@ -967,12 +969,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       }
     } else {
       // closed-form geometries only: plane / conic normal inline
-      ort::propagate(r, t, alpha);
-      ort::add_opd(r, t, n_pre);
-      if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-#ifndef ORT_NO_AP_PROG
-      if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-#endif
+      to_intersection<kApProg>(a, s, r, t, alpha, n_pre);
       double nx, ny, nz;
       if (s.geometry == ORT_GEOM_PLANE) {
         nx = 0.0; ny = 0.0; nz = 1.0;
@@ -988,17 +985,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
     }
     globalize(a, s, r);
     if constexpr ((FEAT & F_REC) != 0) {
-      if ((s.flags & ORT_SURF_RECORD) && active) {
-        double* base = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + rid;
-        ORT_ST(base[0 * a.n_rays], r.x);
-        ORT_ST(base[1 * a.n_rays], r.y);
-        ORT_ST(base[2 * a.n_rays], r.z);
-        ORT_ST(base[3 * a.n_rays], r.L);
-        ORT_ST(base[4 * a.n_rays], r.M);
-        ORT_ST(base[5 * a.n_rays], r.N);
-        ORT_ST(base[6 * a.n_rays], ort::intensity(r));
-        ORT_ST(base[7 * a.n_rays], r.opd);
-      }
+      if ((s.flags & ORT_SURF_RECORD) && active) store_record(a, s, rid, r);
     }
   }
   // real_ray_tracer.py:84-89: image-space propagate by the last surface's thickness
@@ -1110,15 +1097,7 @@ __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam,
   } else {
     if (a.seg) lam = a.seg[a.n_seg == 1 ? 0 : r_ld / a.seg_len].lambda_idx;
     if constexpr ((FEAT & F_WRAY) != 0) wl = a.w[r_ld];
-    r.x = a.in.x[r_ld];
-    r.y = a.in.y[r_ld];
-    r.z = a.in.z[r_ld];
-    r.L = a.in.L[r_ld];
-    r.M = a.in.M[r_ld];
-    r.N = a.in.N[r_ld];
-    r.i = a.in.i[r_ld];
-    r.opd = a.in.opd[r_ld];
-    r.att = 0.0;
+    load_ray(a, r_ld, r);
     // the fast flat-surface refraction assumes finite directions (ort_fastpath.h)
     if constexpr (FAST) bad = bad | !(::fabs(r.L) < __builtin_inf() && ::fabs(r.M) < __builtin_inf());
   }
@@ -1132,16 +1111,8 @@ template <uint32_t FEAT, bool FAST>
 __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, double wl,
                                        int64_t rid, bool active, bool& bad, bool& geom_bad,
                                        double apod = 1.0) {
-#ifdef ORT_PREFETCH_SURF  // (A/B builds) surface si + 1's record loaded during surface si
-  ort_surface s_next = cst(a.surf)[a.start_surface < a.n_surf ? a.start_surface : 0];
-#endif
   for (int si = a.start_surface; si < a.n_surf; ++si) {
-#ifdef ORT_PREFETCH_SURF
-    const ort_surface s = s_next;
-    s_next = cst(a.surf)[si + 1 < a.n_surf ? si + 1 : si];
-#else
     const ort_surface s = cst(a.surf)[si];
-#endif
     const ort_surface_optics o = surface_optics<FEAT>(a, s, lam, si, wl);
     if constexpr ((FEAT & F_AXIAL) != 0)
       r.z = r.z + -s.cs_t[2];  // x + -0 and y + -0 are identities
@@ -1214,18 +1185,10 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     }
     if constexpr ((FEAT & F_REC) != 0) {
       if ((s.flags & ORT_SURF_RECORD) && active) {
-        double* b = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + rid;
-        ORT_ST(b[0 * a.n_rays], r.x);
-        ORT_ST(b[1 * a.n_rays], r.y);
-        ORT_ST(b[2 * a.n_rays], r.z);
-        ORT_ST(b[3 * a.n_rays], r.L);
-        ORT_ST(b[4 * a.n_rays], r.M);
-        ORT_ST(b[5 * a.n_rays], r.N);
         if constexpr ((FEAT & F_GEN) != 0)
-          ORT_ST(b[6 * a.n_rays], a.apod ? apod * ort::intensity(r) : ort::intensity(r));
+          store_record(a, s, rid, r, a.apod ? &apod : nullptr);
         else
-          ORT_ST(b[6 * a.n_rays], ort::intensity(r));
-        ORT_ST(b[7 * a.n_rays], r.opd);
+          store_record(a, s, rid, r);
       }
     }
   }
@@ -1293,14 +1256,7 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
 #endif
   if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(a, r, inten, active);
   if (!active) return;
-  ORT_ST(a.out.x[rid], r.x);
-  ORT_ST(a.out.y[rid], r.y);
-  ORT_ST(a.out.z[rid], r.z);
-  ORT_ST(a.out.L[rid], r.L);
-  ORT_ST(a.out.M[rid], r.M);
-  ORT_ST(a.out.N[rid], r.N);
-  ORT_ST(a.out.i[rid], inten);
-  ORT_ST(a.out.opd[rid], r.opd);
+  store_ray(a, rid, r, &inten);
 }
 
 // Sum over the 64 lanes of a wave. With the whole wave active: DPP row operations
