@@ -90,6 +90,19 @@ int ort_host_huygens_psf(const double* ix, const double* iy, const double* iz, i
                          const double* amp, const double* opd_mm, int64_t n_pupil,
                          double wavelength_mm, double rp, double* psf);
 
+/* ort_irradiance_bin / ort_irradiance_bin_vjp on host memory (added within v3): the kernels' own pixel
+ * search, weights, quantisation and finish (csrc/ort_irradiance.h); the integer sums make the
+ * result independent of the thread count and identical to the device's, bit for bit. Same
+ * argument checks, no workspace. */
+int ort_host_irradiance_bin(const double* x, const double* y, const double* power, int64_t n,
+                            const double* x_edges, int64_t nx, const double* y_edges,
+                            int64_t ny, int32_t mode, double pixel_area, double* out);
+int ort_host_irradiance_bin_vjp(const double* x, const double* y, const double* power,
+                                int64_t n, const double* x_edges, int64_t nx,
+                                const double* y_edges, int64_t ny, double pixel_area,
+                                const double* grad_out, double* grad_x, double* grad_y,
+                                double* grad_power);
+
 /* threads used by the calls (OpenMP; <= 0: the OpenMP default) */
 void ort_host_set_threads(int32_t n);
 

@@ -903,6 +903,69 @@ int ort_huygens_psf(const double* ix, const double* iy, const double* iz, int64_
                     double wavelength_mm, double rp, double* psf, void* workspace,
                     int64_t workspace_size, void* stream);
 
+/* ---- Incoherent irradiance binning (analysis/irradiance.py:243-330; added within v21:
+ * new entry points only, no struct or existing signature changes) ------------------------
+ * The power of n rays (x, y in the detector surface's frame) summed on an nx x ny pixel grid
+ * given by strictly increasing x_edges[nx + 1], y_edges[ny + 1], divided by the pixel area.
+ *
+ * ORT_BIN_HISTOGRAM  numpy.histogram2d(x, y, bins=[x_edges, y_edges], weights=power) after
+ *   the reference's `power > 0` filter. Along each axis the pixel is
+ *   searchsorted(edges, v, side='right') - 1, a value equal to the last edge goes to the last
+ *   bin; rays below the first edge, above the last edge or NaN in x or y are dropped, and so
+ *   are rays with power <= 0 or NaN power. out[ix * ny + iy]: X is the row index.
+ * ORT_BIN_BILINEAR   backend/torch_backend.py:548-599 (get_bilinear_weights) and four
+ *   index_put(accumulate=True): pixel centres c = (e[:-1] + e[1:]) / 2, ix =
+ *   clamp(searchsorted(cx, x, right=True) - 1, 0, nx - 2), wx = (x - cx[ix]) /
+ *   (cx[ix+1] - cx[ix] + 1e-9), the same in y, weights (1-wx)(1-wy), (1-wx)wy, wx(1-wy), wx wy
+ *   on pixels (ix, iy), (ix, iy+1), (ix+1, iy), (ix+1, iy+1), each times power. No power
+ *   filter; rays outside the centres extrapolate with weights outside [0, 1].
+ *   out[iy * nx + ix]: Y is the row index (the reference's two paths differ in this).
+ *   Needs nx, ny >= 2.
+ *
+ * Accumulation is 64-bit fixed point, so a pixel's value depends only on the multiset of
+ * its contributions (bit-identical under any permutation of the rays, grid, stream or
+ * tiling). With cmax the largest finite |contribution| of the call (reduced on the device),
+ *
+ *   ORT_IRRADIANCE_EXPONENT:  E = 62 - ec - L,  cmax = m 2^ec with 0.5 <= m < 1 (frexp),
+ *                             L = the least integer with 2^L >= n;  E = 0 when cmax = 0
+ *
+ * every finite contribution c is rounded to nearest once to q = rint(c 2^E), |q| <=
+ * 2^(62 - L), so the sum of up to n of them stays within 2^62. A pixel's integer sum S
+ * becomes fp64(S) 2^-E / area: one rounding of the sum, then the division. Error bound per
+ * pixel with m contributions: m 2^-(E+1) (quantisation) + 2^-53 |sum| (the conversion), over
+ * the area, plus the division's rounding. A contribution that is not finite (infinite or NaN
+ * power or, bilinear, coordinates) marks its pixel and the pixel reads NaN (the reference
+ * gives +-inf for an infinite power: the one deviation).
+ *
+ * Images of up to ORT_IRRADIANCE_TILE_PIXELS pixels are summed in a private LDS tile per
+ * workgroup (128 KiB of the CU's 160), larger ones with 64-bit integer atomics in L2.
+ * nx * ny <= ORT_IRRADIANCE_MAX_PIXELS, more is ORT_ERR_ARG. */
+enum ort_bin_mode { ORT_BIN_HISTOGRAM = 0, ORT_BIN_BILINEAR = 1 };
+#define ORT_IRRADIANCE_TILE_PIXELS 16384
+#define ORT_IRRADIANCE_MAX_PIXELS 67108864
+
+/* Bytes of device workspace ort_irradiance_bin needs (< 0: ORT_ERR_ARG). */
+int64_t ort_irradiance_workspace_size(int64_t nx, int64_t ny);
+
+/* x, y, power [n], x_edges [nx + 1], y_edges [ny + 1], out [nx * ny]: device doubles.
+ * pixel_area > 0 divides by it; otherwise by the first pixel's area (x_edges[1] -
+ * x_edges[0]) * (y_edges[1] - y_edges[0]), formed on the device. n == 0 writes zeros.
+ * ORT_ERR_ARG for a negative n, null pointers, an unknown mode, sizes outside the limits or a
+ * short workspace. One memset and three launches on `stream`, no synchronisation. */
+int ort_irradiance_bin(const double* x, const double* y, const double* power, int64_t n,
+                       const double* x_edges, int64_t nx, const double* y_edges, int64_t ny,
+                       int32_t mode, double pixel_area, double* out, void* workspace,
+                       int64_t workspace_size, void* stream);
+
+/* ORT_BIN_BILINEAR's vector-Jacobian product: grad_out [ny * nx] is the gradient of a scalar
+ * with respect to `out`; writes its gradient with respect to x, y and power [n] each (the
+ * clamped cell indices are piecewise constant: zero derivative, as in torch). A gather, one
+ * ray per lane, no atomics, one launch. */
+int ort_irradiance_bin_vjp(const double* x, const double* y, const double* power, int64_t n,
+                           const double* x_edges, int64_t nx, const double* y_edges, int64_t ny,
+                           double pixel_area, const double* grad_out, double* grad_x,
+                           double* grad_y, double* grad_power, void* stream);
+
 /* Ray generation only (ray_generator.py:28-106): fills rays_out from pupil points. */
 int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,
                       const ort_batch* batch, void* stream);

@@ -7,11 +7,14 @@ SurfaceGroup / RealRays / SpotDiagram / Wavefront interface.
 """
 
 from . import _abi
-from . import ops  # noqa: F401  (registers torch.ops.ort.trace_sequential / trace_pupil / huygens_psf)
+from . import ops  # noqa: F401  (registers torch.ops.ort.trace_sequential / trace_pupil / huygens_psf /
+# irradiance_bin)
 from .distribution import create_distribution
+from .irradiance import IncoherentIrradiance
 from .materials import IdealMaterial, Material
 from .optic import Optic
 from .psf import HuygensPSF
 
-__all__ = ["Optic", "IdealMaterial", "Material", "HuygensPSF", "create_distribution", "_abi"]
+__all__ = ["Optic", "IdealMaterial", "Material", "HuygensPSF", "IncoherentIrradiance",
+           "create_distribution", "_abi"]
 __version__ = "0.1.0"

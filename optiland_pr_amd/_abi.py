@@ -11,6 +11,10 @@ import numpy as np
 
 ABI_VERSION = 21
 HUYGENS_CHUNK = 512  # ORT_HUYGENS_CHUNK: pupil points per partial sum of ort_huygens_psf
+BIN_HISTOGRAM = 0  # ort_bin_mode
+BIN_BILINEAR = 1
+IRRADIANCE_TILE_PIXELS = 16384  # ORT_IRRADIANCE_TILE_PIXELS: the largest image summed in LDS
+IRRADIANCE_MAX_PIXELS = 1 << 26  # ORT_IRRADIANCE_MAX_PIXELS
 VJP_UNROLLED = 0
 VJP_ADJOINT = 1
 AP_RADIAL = 1
@@ -217,3 +221,17 @@ RAY_FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
 
 VJP_ADJOINT_MAX_SLOTS = 512
 ADJ_HIST = 4  # ort_sweep.h kHist: Newton iterates the adjoint tape keeps per surface  # ORT_VJP_ADJOINT_MAX_SLOTS: 3 S + n_zern + 1 at most
+
+
+def irradiance_exponent(n, cmax):
+    """ORT_IRRADIANCE_EXPONENT (include/optiland_rt.h): the fixed-point sums of
+    ort_irradiance_bin count units of 2^-E, E = 62 - ec - L with cmax = m 2^ec (0.5 <= m < 1)
+    the largest finite |contribution| and L the least integer with 2^L >= n; 0 when cmax is 0."""
+    import math
+
+    if not cmax > 0.0:
+        return 0
+    L = 0
+    while (1 << L) < n:
+        L += 1
+    return 62 - math.frexp(cmax)[1] - L

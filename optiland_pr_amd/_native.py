@@ -156,7 +156,8 @@ EXPORTS = ("ort_abi_version", "ort_trace_sequential", "ort_trace_pupil", "ort_tr
            "ort_wavefront_workspace_size", "ort_wavefront_opd", "ort_patch_zernike",
            "ort_patch_zernike_ptrs", "ort_newton_finish", "ort_adam_patch_zernike",
            "ort_rms_finish", "ort_newton_finish_rms", "ort_huygens_workspace_size",
-           "ort_huygens_psf")
+           "ort_huygens_psf", "ort_irradiance_workspace_size", "ort_irradiance_bin",
+           "ort_irradiance_bin_vjp")
 
 _lib = None
 
@@ -275,6 +276,18 @@ def load(path: str | None = None):
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_void_p]
+    lib.ort_irradiance_workspace_size.restype = C.c_int64
+    lib.ort_irradiance_workspace_size.argtypes = [C.c_int64, C.c_int64]
+    lib.ort_irradiance_bin.restype = C.c_int
+    lib.ort_irradiance_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                       C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]
+    lib.ort_irradiance_bin_vjp.restype = C.c_int
+    lib.ort_irradiance_bin_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
     v = lib.ort_abi_version()
     if v != _abi.ABI_VERSION:
         raise NativeLibraryError(f"ABI version mismatch: library {v}, host {_abi.ABI_VERSION}")
@@ -286,7 +299,8 @@ def load(path: str | None = None):
 HOST_EXPORTS = ("ort_host_abi_version", "ort_host_trace_sequential",
                 "ort_host_trace_sequential_vjp", "ort_host_trace_pupil", "ort_host_trace_pupil_vjp",
                 "ort_host_rms_spot", "ort_host_rms_spot_vjp", "ort_host_set_threads",
-                "ort_host_huygens_psf")
+                "ort_host_huygens_psf", "ort_host_irradiance_bin",
+                "ort_host_irradiance_bin_vjp")
 HOST_ABI_VERSION = 3  # include/optiland_host.h ORT_HOST_ABI_VERSION
 
 _host = None
@@ -334,6 +348,15 @@ def load_host(path: str | None = None):
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p]
+    lib.ort_host_irradiance_bin.restype = C.c_int
+    lib.ort_host_irradiance_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.c_double, C.c_void_p]
+    lib.ort_host_irradiance_bin_vjp.restype = C.c_int
+    lib.ort_host_irradiance_bin_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
     v = lib.ort_host_abi_version()
     if v != HOST_ABI_VERSION:
         raise NativeLibraryError(f"host ABI version mismatch: library {v}, host {HOST_ABI_VERSION}")

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ort_huygens.h"
+#include "ort_irradiance.h"
 #include "ort_sweep.h"
 
 namespace {
@@ -624,6 +625,77 @@ int ort_host_huygens_psf(const double* ix, const double* iy, const double* iz, i
     } while (j0 < n_pupil);
     psf[p] = re * re + im * im;
   }
+  return ORT_OK;
+}
+
+// IncoherentIrradiance's binning (analysis/irradiance.py:243-330) on host memory: the kernels'
+// per-ray pieces (ort_irradiance.h) and their fixed-point sums. Integer adds commute, so the
+// threads may take the rays in any split.
+int ort_host_irradiance_bin(const double* x, const double* y, const double* power, int64_t n,
+                            const double* x_edges, int64_t nx, const double* y_edges,
+                            int64_t ny, int32_t mode, double pixel_area, double* out) {
+  if (mode != ORT_BIN_HISTOGRAM && mode != ORT_BIN_BILINEAR) return ORT_ERR_ARG;
+  const int64_t lo = mode == ORT_BIN_BILINEAR ? 2 : 1;
+  if (n < 0 || nx < lo || ny < lo || nx > ORT_IRRADIANCE_MAX_PIXELS ||
+      ny > ORT_IRRADIANCE_MAX_PIXELS || nx * ny > ORT_IRRADIANCE_MAX_PIXELS)
+    return ORT_ERR_ARG;
+  if (!x_edges || !y_edges || !out || (n > 0 && (!x || !y || !power))) return ORT_ERR_ARG;
+  const ort::IrrGrid g{x_edges, y_edges, nx, ny, mode};
+  const int64_t npix = nx * ny;
+  const int nt = threads_for(n);
+  uint64_t cmax = 0;
+#pragma omp parallel for num_threads(nt) schedule(static) reduction(max : cmax)
+  for (int64_t i = 0; i < n; ++i) {
+    int64_t pix[4];
+    double c[4];
+    const int k = ort::irr_contributions(g, x[i], y[i], power[i], pix, c);
+    for (int j = 0; j < k; ++j)
+      if (ort::irr_finite(c[j])) cmax = std::max(cmax, ort::irr_abs_bits(c[j]));
+  }
+  const int E = ort::irr_exponent(cmax, ort::irr_log2_ceil(n));
+  std::vector<uint64_t> acc((size_t)npix, 0);
+  std::vector<uint32_t> flags((size_t)npix, 0);
+  uint64_t* const sums = acc.data();
+  uint32_t* const marks = flags.data();
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int64_t i = 0; i < n; ++i) {
+    int64_t pix[4];
+    double c[4];
+    const int k = ort::irr_contributions(g, x[i], y[i], power[i], pix, c);
+    for (int j = 0; j < k; ++j) {
+      if (ort::irr_finite(c[j])) {
+        const uint64_t q = (uint64_t)ort::irr_quantise(c[j], E);
+#pragma omp atomic
+        sums[pix[j]] += q;
+      } else {
+#pragma omp atomic write
+        marks[pix[j]] = 1u;
+      }
+    }
+  }
+  const double area = ort::irr_area(g, pixel_area);
+  for (int64_t j = 0; j < npix; ++j)
+    out[j] = ort::irr_finish((int64_t)acc[(size_t)j], flags[(size_t)j], E, area);
+  return ORT_OK;
+}
+
+int ort_host_irradiance_bin_vjp(const double* x, const double* y, const double* power,
+                                int64_t n, const double* x_edges, int64_t nx,
+                                const double* y_edges, int64_t ny, double pixel_area,
+                                const double* grad_out, double* grad_x, double* grad_y,
+                                double* grad_power) {
+  if (n < 0 || nx < 2 || ny < 2 || nx > ORT_IRRADIANCE_MAX_PIXELS ||
+      ny > ORT_IRRADIANCE_MAX_PIXELS || nx * ny > ORT_IRRADIANCE_MAX_PIXELS)
+    return ORT_ERR_ARG;
+  if (!x_edges || !y_edges || !grad_out) return ORT_ERR_ARG;
+  if (n == 0) return ORT_OK;
+  if (!x || !y || !power || !grad_x || !grad_y || !grad_power) return ORT_ERR_ARG;
+  const ort::IrrGrid g{x_edges, y_edges, nx, ny, ORT_BIN_BILINEAR};
+  const double area = ort::irr_area(g, pixel_area);
+  const int nt = threads_for(n);
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int64_t i = 0; i < n; ++i)
+    ort::irr_vjp(g, grad_out, x[i], y[i], power[i], area, grad_x[i], grad_y[i], grad_power[i]);
   return ORT_OK;
 }
 

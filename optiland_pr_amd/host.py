@@ -240,3 +240,27 @@ def huygens_psf(image, pupil, wavelength_mm, rp):
                                   float(wavelength_mm), float(rp), _p(psf))
     _native.check(rc, "ort_host_huygens_psf")
     return psf
+
+
+def irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=0.0):
+    """ort_host_irradiance_bin: the flat map [nx * ny] of contiguous float64 CPU tensors
+    (histogram: index ix * ny + iy; bilinear: iy * nx + ix)."""
+    lib = _native.load_host()
+    nx, ny = x_edges.numel() - 1, y_edges.numel() - 1
+    out = torch.empty(max(nx * ny, 0), dtype=torch.float64)
+    rc = lib.ort_host_irradiance_bin(_p(x), _p(y), _p(power), x.numel(), _p(x_edges), nx,
+                                     _p(y_edges), ny, int(mode), float(pixel_area), _p(out))
+    _native.check(rc, "ort_host_irradiance_bin")
+    return out
+
+
+def irradiance_bin_vjp(x, y, power, x_edges, y_edges, grad, pixel_area=0.0):
+    """ort_host_irradiance_bin_vjp: (g_x, g_y, g_power) of the bilinear map."""
+    lib = _native.load_host()
+    nx, ny = x_edges.numel() - 1, y_edges.numel() - 1
+    gx, gy, gp = (torch.empty(x.numel(), dtype=torch.float64) for _ in range(3))
+    rc = lib.ort_host_irradiance_bin_vjp(_p(x), _p(y), _p(power), x.numel(), _p(x_edges), nx,
+                                         _p(y_edges), ny, float(pixel_area), _p(grad), _p(gx),
+                                         _p(gy), _p(gp))
+    _native.check(rc, "ort_host_irradiance_bin_vjp")
+    return gx, gy, gp

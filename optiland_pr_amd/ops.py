@@ -43,6 +43,13 @@ ort::huygens_psf(image_x, image_y, image_z, pupil_x, pupil_y, pupil_z, amp, opd_
 wavelength_mm, rp) -> psf is HuygensPSF's summation (psf/huygens_fresnel_strategies.py:97-172,
 ort_huygens_psf) on both keys; it has no autograd formula yet and refuses inputs that require
 grad.
+
+ort::irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=None) -> map is
+IncoherentIrradiance's binning (analysis/irradiance.py:243-330, ort_irradiance_bin) on both
+keys: mode _abi.BIN_HISTOGRAM ([nx, ny], numpy.histogram2d's pixels) or _abi.BIN_BILINEAR
+([ny, nx], get_bilinear_weights' splat), fixed-point sums that do not depend on the order of
+the rays. The bilinear mode is differentiable in x, y and power through
+ort::irradiance_bin_vjp (a gather); the histogram mode refuses inputs that require grad.
 """
 
 from __future__ import annotations
@@ -1057,3 +1064,181 @@ def _huygens_backward(ctx, grad):
 
 
 huygens_psf.register_autograd(_huygens_backward, setup_context=_huygens_setup)
+
+
+# --------------------------------------------------------------------------------------
+# ort::irradiance_bin -- IncoherentIrradiance's binning (analysis/irradiance.py:243-330)
+# --------------------------------------------------------------------------------------
+def _check_irradiance_inputs(x, y, power, x_edges, y_edges, mode, op="ort::irradiance_bin"):
+    """What the kernels assume of the shapes (no data is read: the fake kernels run this
+    too). Returns (nx, ny)."""
+    for t in (x, y, power, x_edges, y_edges):
+        if t.dtype != torch.float64:
+            raise ValueError(f"{op}: every tensor must be float64 (got {t.dtype})")
+        if t.device != x.device:
+            raise ValueError(f"{op}: tensors on {x.device} and {t.device}")
+    if not (x.numel() == y.numel() == power.numel()):
+        raise ValueError(f"{op}: x, y, power of different lengths "
+                         f"({x.numel()}, {y.numel()}, {power.numel()})")
+    if x_edges.dim() != 1 or y_edges.dim() != 1:
+        raise ValueError(f"{op}: x_edges and y_edges must be one-dimensional")
+    if mode not in (_abi.BIN_HISTOGRAM, _abi.BIN_BILINEAR):
+        raise ValueError(f"{op}: mode must be BIN_HISTOGRAM (0) or BIN_BILINEAR (1), got {mode}")
+    nx, ny = x_edges.numel() - 1, y_edges.numel() - 1
+    lo = 2 if mode == _abi.BIN_BILINEAR else 1
+    if nx < lo or ny < lo:
+        raise ValueError(f"{op}: needs at least {lo} pixel(s) along each axis in this mode "
+                         f"(got {nx} x {ny})")
+    if nx * ny > _abi.IRRADIANCE_MAX_PIXELS:
+        raise ValueError(f"{op}: {nx} x {ny} pixels exceed the supported "
+                         f"{_abi.IRRADIANCE_MAX_PIXELS}")
+    return nx, ny
+
+
+_edges_checked = {}  # id(tensor) -> (weakref, version): edge tensors already found increasing
+
+
+def _check_edges_increasing(op, *edges):
+    """Strictly increasing edges (NaN fails). The comparison reads device data, so a tensor
+    that passed is remembered by identity and version: repeated calls on the same edge
+    tensors (a loop over fields, an optimisation) do not synchronise again."""
+    for e in edges:
+        hit = _edges_checked.get(id(e))
+        if hit is not None and hit[0]() is e and hit[1] == e._version:
+            continue
+        if not bool(torch.all(e[1:] > e[:-1])):
+            raise ValueError(f"{op}: edges must be strictly increasing")
+        if len(_edges_checked) >= 64:
+            _edges_checked.clear()
+        _edges_checked[id(e)] = (weakref.ref(e), e._version)
+
+
+def _irr_shape(nx, ny, mode):
+    return (nx, ny) if mode == _abi.BIN_HISTOGRAM else (ny, nx)
+
+
+@torch.library.custom_op("ort::irradiance_bin", mutates_args=(), device_types="cuda")
+def irradiance_bin(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
+                   x_edges: torch.Tensor, y_edges: torch.Tensor, mode: int,
+                   pixel_area: float | None = None) -> torch.Tensor:
+    """ort_irradiance_bin on the current stream: the power of the rays at (x, y) (the
+    detector's frame) summed per pixel and divided by the pixel area (None: the first
+    pixel's, from the edges). BIN_HISTOGRAM returns [nx, ny] (X is the row index, as
+    numpy.histogram2d), BIN_BILINEAR [ny, nx] (Y is the row index, as the reference's
+    index_put): the reference's two paths differ in orientation and so do these."""
+    from .raytrace import _ptr, _stream_handle
+
+    lib = _native.load()
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, mode)
+    _check_edges_increasing("ort::irradiance_bin", x_edges, y_edges)
+    fx, fy, fp, ex, ey = _flat((x, y, power, x_edges, y_edges))
+    size = int(lib.ort_irradiance_workspace_size(nx, ny))
+    _native.check(size if size < 0 else 0, "ort_irradiance_workspace_size")
+    ws = torch.empty(size, dtype=torch.uint8, device=x.device)
+    out = torch.empty(nx * ny, dtype=torch.float64, device=x.device)
+    rc = lib.ort_irradiance_bin(_ptr(fx), _ptr(fy), _ptr(fp), fx.numel(), _ptr(ex), nx,
+                                _ptr(ey), ny, int(mode), float(pixel_area or 0.0), _ptr(out),
+                                _ptr(ws), size, _stream_handle())
+    _native.check(rc, "ort_irradiance_bin")
+    return out.reshape(_irr_shape(nx, ny, mode))
+
+
+@irradiance_bin.register_kernel("cpu")
+def _irradiance_bin_cpu(x, y, power, x_edges, y_edges, mode, pixel_area=None):
+    """The CPU dispatch key: the same pixels, quantisation and finish in the host library."""
+    from . import host
+
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, mode)
+    _check_edges_increasing("ort::irradiance_bin", x_edges, y_edges)
+    out = host.irradiance_bin(*_flat((x, y, power, x_edges, y_edges)), mode,
+                              float(pixel_area or 0.0))
+    return out.reshape(_irr_shape(nx, ny, mode))
+
+
+@irradiance_bin.register_fake
+def _(x, y, power, x_edges, y_edges, mode, pixel_area=None):
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, mode)
+    return x.new_empty(_irr_shape(nx, ny, mode), dtype=torch.float64)
+
+
+def _check_irradiance_grad(grad, nx, ny, device):
+    if grad.dtype != torch.float64 or grad.device != device or grad.shape != (ny, nx):
+        raise ValueError(f"ort::irradiance_bin_vjp: grad must be a float64 [{ny}, {nx}] tensor "
+                         f"on {device} (got {grad.dtype} {tuple(grad.shape)} on {grad.device})")
+
+
+@torch.library.custom_op("ort::irradiance_bin_vjp", mutates_args=(), device_types="cuda")
+def irradiance_bin_vjp(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
+                       x_edges: torch.Tensor, y_edges: torch.Tensor, grad: torch.Tensor,
+                       pixel_area: float | None = None
+                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ort_irradiance_bin_vjp: the gradients of a scalar with respect to x, y and power, given
+    its gradient `grad` [ny, nx] with respect to the BIN_BILINEAR map."""
+    from .raytrace import _ptr, _stream_handle
+
+    lib = _native.load()
+    op = "ort::irradiance_bin_vjp"
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, _abi.BIN_BILINEAR, op)
+    _check_irradiance_grad(grad, nx, ny, x.device)
+    _check_edges_increasing(op, x_edges, y_edges)
+    fx, fy, fp, ex, ey, fg = _flat((x, y, power, x_edges, y_edges, grad))
+    gx, gy, gp = (torch.empty(fx.numel(), dtype=torch.float64, device=x.device)
+                  for _ in range(3))
+    rc = lib.ort_irradiance_bin_vjp(_ptr(fx), _ptr(fy), _ptr(fp), fx.numel(), _ptr(ex), nx,
+                                    _ptr(ey), ny, float(pixel_area or 0.0), _ptr(fg),
+                                    _ptr(gx), _ptr(gy), _ptr(gp), _stream_handle())
+    _native.check(rc, op)
+    return gx.reshape(x.shape), gy.reshape(y.shape), gp.reshape(power.shape)
+
+
+@irradiance_bin_vjp.register_kernel("cpu")
+def _irradiance_bin_vjp_cpu(x, y, power, x_edges, y_edges, grad, pixel_area=None):
+    from . import host
+
+    op = "ort::irradiance_bin_vjp"
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, _abi.BIN_BILINEAR, op)
+    _check_irradiance_grad(grad, nx, ny, x.device)
+    _check_edges_increasing(op, x_edges, y_edges)
+    gx, gy, gp = host.irradiance_bin_vjp(*_flat((x, y, power, x_edges, y_edges, grad)),
+                                         float(pixel_area or 0.0))
+    return gx.reshape(x.shape), gy.reshape(y.shape), gp.reshape(power.shape)
+
+
+@irradiance_bin_vjp.register_fake
+def _(x, y, power, x_edges, y_edges, grad, pixel_area=None):
+    nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, _abi.BIN_BILINEAR,
+                                      "ort::irradiance_bin_vjp")
+    _check_irradiance_grad(grad, nx, ny, x.device)
+    return (x.new_empty(x.shape, dtype=torch.float64), y.new_empty(y.shape, dtype=torch.float64),
+            power.new_empty(power.shape, dtype=torch.float64))
+
+
+_IRRADIANCE_NO_GRAD = ("ort::irradiance_bin: the histogram mode (BIN_HISTOGRAM) is piecewise "
+                       "constant in x, y and is not differentiable; use the bilinear mode "
+                       "(BIN_BILINEAR) for inputs that require grad, or detach them")
+
+
+def _irradiance_setup(ctx, inputs, output):
+    x, y, power, x_edges, y_edges, mode, pixel_area = inputs
+    if mode != _abi.BIN_BILINEAR:
+        # refuse in the forward, as ort::huygens_psf does: a map that silently dropped its
+        # graph would give a loss built on it a zero gradient
+        if any(ctx.needs_input_grad):
+            raise NotImplementedError(_IRRADIANCE_NO_GRAD)
+        return
+    if any(ctx.needs_input_grad[3:5]):
+        raise NotImplementedError("ort::irradiance_bin: no gradient with respect to the edges")
+    ctx.save_for_backward(x, y, power, x_edges, y_edges)
+    ctx.pixel_area = pixel_area
+
+
+def _irradiance_backward(ctx, grad):
+    x, y, power, x_edges, y_edges = ctx.saved_tensors
+    gx, gy, gp = torch.ops.ort.irradiance_bin_vjp(x, y, power, x_edges, y_edges,
+                                                  grad.contiguous(), ctx.pixel_area)
+    need = ctx.needs_input_grad
+    return (gx if need[0] else None, gy if need[1] else None, gp if need[2] else None,
+            None, None, None, None)
+
+
+irradiance_bin.register_autograd(_irradiance_backward, setup_context=_irradiance_setup)
