@@ -56,8 +56,28 @@ namespace fast {
 // checks to measure what they cost
 #ifdef ORT_FAST_NOCHECK
 #define ORT_CHK(bad, cond) ((void)0)
+#define ORT_CHK_UNIFORM(bad, cond) ((void)0)
 #else
-#define ORT_CHK(bad, cond) ((bad) = (bad) | (cond))
+#define ORT_CHK(bad, cond) ::ort::fast::chk((bad), (cond))
+#define ORT_CHK_UNIFORM(bad, cond) ::ort::fast::chk_uniform((bad), (cond))
+#endif
+
+// The flag a sequence ORs its range failures into (the functions' class B): a per-lane
+// bool, or WaveFlag, the same flags of a whole wave as a mask (bit = lane). A loop that
+// carries a bool across uniform branches keeps it in a vector register and converts it
+// to a lane mask and back at every join; the mask is wave-uniform, so it lives in scalar
+// registers (the closed-form kernel's surface loop, which ORs each surface's bool in once).
+struct WaveFlag {
+  uint64_t m;
+};
+ORT_INLINE void chk(bool& bad, bool cond) { bad = bad | cond; }
+// a wave-uniform condition (a lens constant)
+ORT_INLINE void chk_uniform(bool& bad, bool cond) { bad = bad | cond; }
+#if defined(__HIPCC__)  // device code only: there is no wave on the host
+__device__ inline void chk(WaveFlag& bad, bool cond) { bad.m |= __builtin_amdgcn_ballot_w64(cond); }
+__device__ inline void chk_uniform(WaveFlag& bad, bool cond) {
+  if (cond) bad.m = ~0ull;
+}
 #endif
 
 ORT_INLINE bool is_pos_zero(double v) {
@@ -69,7 +89,8 @@ ORT_INLINE bool is_pos_zero(double v) {
 }
 
 // sqrt(x) for 2^-767 <= x < inf (ort_core.h sqrt)
-ORT_INLINE double sqrt(double x, bool& bad) {
+template <class B>
+ORT_INLINE double sqrt(double x, B& bad) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y;
@@ -91,7 +112,8 @@ ORT_INLINE double sqrt(double x, bool& bad) {
 
 // sqrt(x) where x >= 1 unless NaN (sums of squares plus 1): only the upper bound could
 // fail, and +inf / NaN give NaN, which state_ok catches: no test
-ORT_INLINE double sqrt_ge1(double x, bool& bad) {
+template <class B>
+ORT_INLINE double sqrt_ge1(double x, B& bad) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y;
@@ -111,7 +133,8 @@ ORT_INLINE double sqrt_ge1(double x, bool& bad) {
 #endif
 }
 
-ORT_INLINE SharedDiv shared_div(double b, bool& bad) {
+template <class B>
+ORT_INLINE SharedDiv shared_div(double b, B& bad) {
   SharedDiv d;
   d.b = b;
   d.ok = true;
@@ -142,7 +165,8 @@ ORT_INLINE SharedDiv shared_div(double b, bool& bad) {
 // overflowed, +inf, whose zero reciprocal makes every quotient NaN for state_ok; NaN
 // likewise. Round 6: the b <= 2^300 test this had was one of those that cannot fail on a
 // finite result.)
-ORT_INLINE SharedDiv shared_div_ge1(double b, bool& bad) {
+template <class B>
+ORT_INLINE SharedDiv shared_div_ge1(double b, B& bad) {
   SharedDiv d;
   d.b = b;
   d.ok = true;
@@ -192,25 +216,29 @@ ORT_INLINE double quot_pos(double a, const SharedDiv& d) {
 ORT_INLINE bool num_ok(double a) { return ::fabs(a) >= 0x1p-300; }
 
 // a / b, |a| >= 2^-300
-ORT_INLINE double sdiv(double a, const SharedDiv& d, bool& bad) {
+template <class B>
+ORT_INLINE double sdiv(double a, const SharedDiv& d, B& bad) {
   ORT_CHK(bad, !num_ok(a));
   return quot(a, d);
 }
 // a / b, |a| >= 2^-300 or a == +0 (coordinates on a symmetry plane)
-ORT_INLINE double sdiv0(double a, const SharedDiv& d, bool& bad) {
+template <class B>
+ORT_INLINE double sdiv0(double a, const SharedDiv& d, B& bad) {
   ORT_CHK(bad, !(num_ok(a) || is_pos_zero(a)));
   return quot(a, d);
 }
 
 // a / b as one IEEE division
-ORT_INLINE double div(double a, double b, bool& bad) {
+template <class B>
+ORT_INLINE double div(double a, double b, B& bad) {
   const SharedDiv d = shared_div(b, bad);
   return sdiv0(a, d, bad);
 }
 
 // rays/ray_generator.py:71-106 + fields/field_types.py:160-181 (ort_core.h generate_ray)
+template <class B>
 ORT_INLINE Ray generate_ray(const ort_segment& s, double px, double py,
-                            const ort_apodization* apod, bool& bad) {
+                            const ort_apodization* apod, B& bad) {
   Ray r;
   double x0, y0;
   if (s.mode == ORT_GEN_INFINITE) {
@@ -260,9 +288,12 @@ ORT_INLINE bool state_ok(const Ray& r) {
 }
 
 // plane.py:61-77 (-z / N) and the plane branch of standard.py:100-103
-ORT_INLINE double distance_plane(const Ray& r, bool& bad) { return div(-r.z, r.N, bad); }
+template <class B>
+ORT_INLINE double distance_plane(const Ray& r, B& bad) { return div(-r.z, r.N, bad); }
 
-// standard.py:89-140 (ort_core.h distance_conic); s.two_r = 2 R formed on the host
+// standard.py:89-140 (ort_core.h distance_conic); s.two_r = 2 R formed on the host.
+// The Newton kernels' form; distance_conic_folded below is the closed-form kernel's copy
+// with the powers of two folded out: a change here belongs there too.
 ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius_inf,
                                  bool& bad) {
   if (radius_inf) {
@@ -296,11 +327,74 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
   return ::fabs(z1) <= ::fabs(zz2) ? t1 : t2;
 }
 
+// distance_conic with the powers of two folded out of the quadratic, for the closed-form
+// kernel (three multiplications and one subtraction fewer per conic); the Newton kernels
+// keep distance_conic above, and a change to either belongs in both. With
+// S = L x + M y - N R + N z the reference forms
+//   b = 2 S, d = b b - (4 a) c, sd = sqrt(d), t = (-b +- sd) / (2 a);
+// this forms
+//   d' = S S - a c, sd' = sqrt(d'), t = (-S +- sd') / a.
+// Multiplying by 2 or 4 is exact and commutes with the rounding of every product, sum and
+// correctly rounded square root it passes through as long as no value involved underflows
+// or overflows, so d = 4 d', sd = 2 sd', -b +- sd = 2 (-S +- sd') and the two quotients
+// are roundings of the same real numbers: t is the reference's bit for bit. Where that
+// premise can fail the lane is flagged:
+//   overflow:  b b or (4 a) c may be infinite with S S, a c finite only when S S or |a c|
+//              >= 2^1022; both are tested against 2^1020 (then 4 |S S - a c| < 2^1023 too).
+//   underflow: a product S S or a c below 2^-1022 is rounded on the subnormal grid and may
+//              differ from a quarter of its scaled twin by up to 2^-1075. If the other
+//              product is >= 2^-960 that is under 2^-60 of its ulp and both differences
+//              round to the other product alone; otherwise |d'| < 2^-959, which fails
+//              sqrt's own lower bound 2^-767. A difference that is itself subnormal fails
+//              that bound as well.
+// The remaining tests are the reference sequence's on the rescaled operands: d' >= 2^-767
+// (d >= 2^-765), |a| <= 2^300 (the divisor range itself; 2 a <= 2^300 was tested before),
+// |-S +- sd'| >= 2^-300.
+// k == 0: the reference's c starts (0.0 - 2R z) + x x. 0.0 - p is -p unless p is a zero,
+// where it is +0 and -p may be -0; x x is >= +0 or NaN, and (+-0) + (+0) = +0,
+// (+-0) + w = w: x x - p is the same value.
+template <class B>
+ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool radius_inf,
+                                        B& bad) {
+  if (radius_inf) {
+    const double Ns = ::fabs(r.N) > 1e-14 ? r.N : 1e-14;
+    return div(-r.z, Ns, bad);
+  }
+  const double R = s.radius, k = s.conic;
+  const double N2 = r.N * r.N;
+  const double z2 = r.z * r.z;
+  double a, S, c;
+  if (k == 0.0) {
+    a = r.L * r.L + r.M * r.M + N2;
+    S = r.L * r.x + r.M * r.y - r.N * R + r.N * r.z;
+    c = r.x * r.x - ORT_TWO_R(s) * r.z + r.y * r.y + z2;
+  } else {
+    a = k * N2 + r.L * r.L + r.M * r.M + N2;
+    S = k * r.N * r.z + r.L * r.x + r.M * r.y - r.N * R + r.N * r.z;
+    c = k * z2 - ORT_TWO_R(s) * r.z + r.x * r.x + r.y * r.y + z2;
+  }
+  const double SS = S * S, ac = a * c;
+  ORT_CHK(bad, !(SS < 0x1p1020 && ::fabs(ac) < 0x1p1020));
+  const double d = SS - ac;
+  const double sd = sqrt(d, bad);
+  const SharedDiv a1 = shared_div(a, bad);
+  // nonzero numerators (checked): quot_pos and quot agree for either sign of a
+  const double n1 = -S + sd, n2 = -S - sd;
+  ORT_CHK(bad, !(num_ok(n1) && num_ok(n2)));
+  const double t1 = quot_pos(n1, a1);
+  const double t2 = quot_pos(n2, a1);
+  const double z1 = r.z + t1 * r.N;
+  const double zz2 = r.z + t2 * r.N;
+  // a == 0 (the -c / b branch, standard.py:138) fails shared_div's range test
+  return ::fabs(z1) <= ::fabs(zz2) ? t1 : t2;
+}
+
 // standard.py:154-167 with the host's inv_r2 = RN(1 / (R * R)) (ort_core.h
 // normal_conic_rcp: the Markstein-corrected quotient needs no range check of its own --
 // r^2 = 0 / inf / NaN give the reference's 1 - q)
+template <class B>
 ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, double& nx,
-                                 double& ny, double& nz, bool& bad) {
+                                 double& ny, double& nz, B& bad) {
   const double r2 = x * x + y * y;
   const double a = ORT_ONE_PLUS_K(s) * r2;
   const double q0 = a * s.inv_r2;
@@ -322,7 +416,8 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, doubl
 // rays/real_rays.py:511-547 (ort_core.h align_normal) for dot != 0: sign(dot) is +-1 and
 // n * sign(dot) is n with its sign bit flipped when dot < 0 -- the same bits as the
 // product; dot == 0 (sign 0) and NaN take the exact path
-ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz, bool& bad) {
+template <class B>
+ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz, B& bad) {
 #ifdef ORT_NO_SIGN_XOR
   return ::ort::align_normal(r, nx, ny, nz);
 #endif
@@ -336,8 +431,9 @@ ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz,
 }
 
 // rays/real_rays.py:141-163 (ort_core.h refract); u_sq = RN(u * u) from the host table
+template <class B>
 ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, double u_sq,
-                        bool& bad) {
+                        B& bad) {
   const double dot = align_normal(r, nx, ny, nz, bad);
   const double root = sqrt(1.0 - ORT_U_SQ(u, u_sq) * (1.0 - dot * dot), bad);
   const double L0 = r.L, M0 = r.M, N0 = r.N;
@@ -355,7 +451,8 @@ ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, doubl
 //   N' = (u N + sign(N) root) - (u sign(N)) |N| = (u N + sign(N) root) - u N.
 // N == 0 / NaN takes the exact path; a non-finite L or M only reaches here on a ray that
 // already failed a check (or came in non-finite, which closed_ray_in flags).
-ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, bool& bad) {
+template <class B>
+ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, B& bad) {
   ORT_CHK(bad, !(::fabs(r.N) > 0.0));
   const double root = sqrt(1.0 - ORT_U_SQ(u, u_sq) * (1.0 - r.N * r.N), bad);
   const double uN = u * r.N;

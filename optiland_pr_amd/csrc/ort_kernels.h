@@ -1078,9 +1078,10 @@ __global__ __launch_bounds__(kBlock) ORT_TRACE_OCC void trace_kernel(const KArgs
 // re-traces on the exact path only the lanes whose `bad` is set (operands outside the
 // ranges where the short sequences are the IEEE results: NaN / missed rays, zeros, ...),
 // so every output is the exact path's.
-template <uint32_t FEAT, bool FAST>
+// B: the range-failure flag of the FAST sequences (ort_fastpath.h: the kernel's WaveFlag)
+template <uint32_t FEAT, bool FAST, class B>
 __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam, double& wl,
-                                         bool& bad) {
+                                         B& bad) {
   ort::Ray r;
   if constexpr ((FEAT & F_GEN) != 0) {
     const int64_t sidx = a.n_seg == 1 ? 0 : r_ld / a.seg_len;
@@ -1099,7 +1100,7 @@ __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam,
     if constexpr ((FEAT & F_WRAY) != 0) wl = a.w[r_ld];
     load_ray(a, r_ld, r);
     // the fast flat-surface refraction assumes finite directions (ort_fastpath.h)
-    if constexpr (FAST) bad = bad | !(::fabs(r.L) < __builtin_inf() && ::fabs(r.M) < __builtin_inf());
+    if constexpr (FAST) ORT_CHK(bad, !(::fabs(r.L) < __builtin_inf() && ::fabs(r.M) < __builtin_inf()));
   }
   return r;
 }
@@ -1107,9 +1108,9 @@ __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam,
 // apod: F_GEN | F_REC with an apodization, the pupil factor of this ray, multiplied into
 // every recorded intensity (the generated ray would carry it from the start,
 // ray_generator.py:91-95); 1 otherwise
-template <uint32_t FEAT, bool FAST>
+template <uint32_t FEAT, bool FAST, class B>
 __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, double wl,
-                                       int64_t rid, bool active, bool& bad, bool& geom_bad,
+                                       int64_t rid, bool active, B& bad, bool& geom_bad,
                                        double apod = 1.0) {
   for (int si = a.start_surface; si < a.n_surf; ++si) {
     const ort_surface s = cst(a.surf)[si];
@@ -1120,16 +1121,22 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
       localize(a, s, r);
     const bool is_plane = s.geometry == ORT_GEOM_PLANE;
     const bool radius_inf = (s.flags & ORT_SURF_RADIUS_INF) != 0;
+    // FAST: this surface's range failures. A per-lane bool inside the surface (the
+    // branches below are uniform, so it stays a lane mask in scalar registers) that is
+    // ORed into the wave mask `bad` once, at the end of the surface: the value the loop
+    // carries is then wave-uniform, where a loop-carried bool is moved into a vector
+    // register and back at every surface.
+    bool sbad = false;
     double t;
     if constexpr (FAST) {
-      t = is_plane ? ort::fast::distance_plane(r, bad)
-                   : ort::fast::distance_conic(r, s, radius_inf, bad);
+      t = is_plane ? ort::fast::distance_plane(r, sbad)
+                   : ort::fast::distance_conic_folded(r, s, radius_inf, sbad);
     } else {
       t = is_plane ? ort::distance_plane(r) : ort::distance_conic(r, s.radius, s.conic, radius_inf);
     }
     if constexpr (FAST) {
       // not a closed-form id: a uniform test, left to the exact pass (below)
-      ORT_CHK(bad, s.geometry > ORT_GEOM_STANDARD || s.geometry < ORT_GEOM_PLANE);
+      ORT_CHK_UNIFORM(bad, s.geometry > ORT_GEOM_STANDARD || s.geometry < ORT_GEOM_PLANE);
     } else if (!is_plane && s.geometry != ORT_GEOM_STANDARD) {  // NaN rays + status
       t = __builtin_nan("");
       geom_bad = true;
@@ -1154,14 +1161,14 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     constexpr bool kFlat = false;
 #endif
     if (kFlat && !refl && (is_plane || radius_inf)) {
-      ort::fast::refract_flat(r, o.u, o.u_sq, bad);  // normal (0, 0, +-1): reduced exactly
+      ort::fast::refract_flat(r, o.u, o.u_sq, sbad);  // normal (0, 0, +-1): reduced exactly
     } else {
       double nx, ny, nz;
       if (is_plane) {
         nx = 0.0; ny = 0.0; nz = 1.0;
       } else if (s.flags & ORT_SURF_INV_R2) {
         if constexpr (FAST)
-          ort::fast::normal_conic_rcp(r.x, r.y, s, nx, ny, nz, bad);
+          ort::fast::normal_conic_rcp(r.x, r.y, s, nx, ny, nz, sbad);
         else
           ort::normal_conic_rcp(r.x, r.y, s.radius, s.conic, s.inv_r2, nx, ny, nz);
       } else {
@@ -1171,18 +1178,28 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
         ort::reflect(r, nx, ny, nz);
       } else {
         if constexpr (FAST)
-          ort::fast::refract(r, nx, ny, nz, o.u, o.u_sq, bad);
+          ort::fast::refract(r, nx, ny, nz, o.u, o.u_sq, sbad);
         else
           ort::refract(r, nx, ny, nz, o.u);
       }
     }
     if constexpr ((FEAT & F_AXIAL) != 0) {
-      r.x = r.x + 0.0;  // the reference's translate by +cs_t (= +0): -0 becomes +0
-      r.y = r.y + 0.0;
+      // the reference's translate by +cs_t (= +0): -0 becomes +0. FAST: only at the first
+      // traced surface. From then on x is not -0 when a surface starts, and the one write
+      // to it, x + t L, is -0 only when both terms are (round to nearest: a zero sum of
+      // terms of unlike sign, or of two +0, is +0), so x + 0.0 has nothing left to change;
+      // y likewise. The incoming ray (the caller's, or a generated one whose offsets can
+      // be -0) keeps the addition.
+      if (!FAST || si == a.start_surface) {
+        if constexpr (FAST) asm volatile("");  // a branch, not two selects per surface
+        r.x = r.x + 0.0;
+        r.y = r.y + 0.0;
+      }
       r.z = r.z + s.cs_t[2];
     } else {
       globalize(a, s, r);
     }
+    if constexpr (FAST) ORT_CHK(bad, sbad);
     if constexpr ((FEAT & F_REC) != 0) {
       if ((s.flags & ORT_SURF_RECORD) && active) {
         if constexpr ((FEAT & F_GEN) != 0)
@@ -1194,8 +1211,26 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
   }
 }
 
+// The kernel's arguments read again from the kernarg segment. The compiler holds every
+// argument a later part of the kernel uses in scalar registers from the first load on; the
+// closed-form kernel's surface loop has none to spare, so what only the code behind the
+// loop reads (output pointers, the exact re-trace's needs) was parked in the lanes of a
+// vector register before the loop and fetched back behind it. Reading the arguments through
+// a pointer the compiler cannot connect to the first loads makes them scalar loads where
+// they are used. Depends on KArgs being the kernel's first explicit argument (kernarg
+// offset 0): see trace_closed_kernel's signature. Should a compiler connect the loads
+// again nothing breaks but the parking returns (tools/isa_stats.py --dump shows
+// v_writelane / v_readlane around the surface loop of <592u>).
+__device__ inline const KArgs& kernarg_again() {
+  auto p = (const __attribute__((address_space(4))) KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (const KArgs&)*p;
+}
+
+// KArgs must stay the first explicit argument: kernarg_again() reads it at kernarg offset 0
 template <uint32_t FEAT>
-__global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8))) void trace_closed_kernel(const KArgs a) {
+__global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8))) void trace_closed_kernel(const KArgs a0) {
+  const KArgs& a = a0;
   int64_t rid;
   bool active;
   if constexpr ((FEAT & F_SPOT) != 0) {  // pair-aligned chunks (KArgs.spot_part1)
@@ -1222,23 +1257,30 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
     }
   }
 #ifndef ORT_NO_DEFERRED_CHECKS
-  ort::Ray r = closed_ray_in<FEAT, true>(a, r_ld, lam, wl, bad);
-  closed_surfaces<FEAT, true>(a, r, lam, wl, rid, active, bad, geom_bad, apod_f);
-  bad = bad | !ort::fast::state_ok(r);  // the upper-range failures (ort_fastpath.h)
+  ort::fast::WaveFlag fbad{0};  // the fast pass's range failures, one bit per lane
+  ort::Ray r = closed_ray_in<FEAT, true>(a, r_ld, lam, wl, fbad);
+  closed_surfaces<FEAT, true>(a, r, lam, wl, rid, active, fbad, geom_bad, apod_f);
+  const KArgs& b = kernarg_again();
+  // and the upper-range failures (ort_fastpath.h); ORT_OPT_EXACT: every lane takes the
+  // exact re-trace, so a launch with it stores the exact path's bits alone (the tests
+  // compare them with a default launch's)
+  bad = ((fbad.m >> (threadIdx.x & 63)) & 1) != 0 || !ort::fast::state_ok(r) ||
+        b.exact_only != 0;
   if (__builtin_expect(bad, 0)) {  // this lane left the fast path's ranges: exact re-trace
-    r = closed_ray_in<FEAT, false>(a, r_ld, lam, wl, bad);
-    closed_surfaces<FEAT, false>(a, r, lam, wl, rid, active, bad, geom_bad, apod_f);
+    r = closed_ray_in<FEAT, false>(b, r_ld, lam, wl, bad);
+    closed_surfaces<FEAT, false>(b, r, lam, wl, rid, active, bad, geom_bad, apod_f);
   }
 #else
-  ort::Ray r = closed_ray_in<FEAT, false>(a, r_ld, lam, wl, bad);
-  closed_surfaces<FEAT, false>(a, r, lam, wl, rid, active, bad, geom_bad, apod_f);
+  const KArgs& b = a;
+  ort::Ray r = closed_ray_in<FEAT, false>(b, r_ld, lam, wl, bad);
+  closed_surfaces<FEAT, false>(b, r, lam, wl, rid, active, bad, geom_bad, apod_f);
 #endif
-  if (a.final_mat >= 0) ort::propagate(r, a.final_thickness, final_alpha<FEAT>(a, lam, wl));
-  if (geom_bad && a.status && threadIdx.x == 0) atomicOr(a.status, (int)ORT_STATUS_BAD_GEOMETRY);
+  if (b.final_mat >= 0) ort::propagate(r, b.final_thickness, final_alpha<FEAT>(b, lam, wl));
+  if (geom_bad && b.status && threadIdx.x == 0) atomicOr(b.status, (int)ORT_STATUS_BAD_GEOMETRY);
   if constexpr ((FEAT & F_GEN) != 0) {
-    if (a.apod && a.status && threadIdx.x == 0 &&
-        (uint32_t)cst(a.apod)->kind > (uint32_t)ORT_APOD_TUKEY)
-      atomicOr(a.status, (int)ORT_STATUS_BAD_APODIZATION);
+    if (b.apod && b.status && threadIdx.x == 0 &&
+        (uint32_t)cst(b.apod)->kind > (uint32_t)ORT_APOD_TUKEY)
+      atomicOr(b.status, (int)ORT_STATUS_BAD_APODIZATION);
   }
   double inten = ort::intensity(r);
 #ifndef ORT_NO_APOD
@@ -1247,16 +1289,16 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
     // trace only ever multiplies the intensity (absorption) or zeroes it (clipping), so
     // apod * (1 * e^att or 0) is the value the ray would carry from an apodized start,
     // with the apodization code outside the traced loop.
-    if (a.apod) {
-      const int64_t sidx = a.n_seg == 1 ? 0 : r_ld / a.seg_len;
-      const int64_t p = a.pupil_per_ray ? r_ld : (r_ld - sidx * a.seg_len);
-      inten = ort::apodize(*cst(a.apod), a.px[p], a.py[p]) * inten;
+    if (b.apod) {
+      const int64_t sidx = b.n_seg == 1 ? 0 : r_ld / b.seg_len;
+      const int64_t p = b.pupil_per_ray ? r_ld : (r_ld - sidx * b.seg_len);
+      inten = ort::apodize(*cst(b.apod), b.px[p], b.py[p]) * inten;
     }
   }
 #endif
-  if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(a, r, inten, active);
+  if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(b, r, inten, active);
   if (!active) return;
-  store_ray(a, rid, r, &inten);
+  store_ray(b, rid, r, &inten);
 }
 
 // Sum over the 64 lanes of a wave. With the whole wave active: DPP row operations

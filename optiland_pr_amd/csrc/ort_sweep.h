@@ -129,7 +129,8 @@ struct KArgs {
   // nullable: the launch is a no-op unless *run_if == 1 (ort_options.run_if)
   const int32_t* run_if;
   int32_t no_init;  // host side only: ORT_OPT_NO_INIT (skip init_outputs)
-  int32_t exact_only;  // ORT_OPT_EXACT: no deferred-check pass (trace_kernel)
+  int32_t exact_only;  // ORT_OPT_EXACT: every ray on the exact sequences (trace_kernel skips
+                       // its deferred-check pass, trace_closed_kernel re-traces every lane)
   // verify-and-re-trace (ort_options.verify_*): the launch decides from vstats first
   const ort_newton_stat* vstats;
   const int32_t* vprev;
