@@ -103,6 +103,25 @@ int ort_host_irradiance_bin_vjp(const double* x, const double* y, const double* 
                                 const double* grad_out, double* grad_x, double* grad_y,
                                 double* grad_power);
 
+/* ort_trace_pupil_polarized / ort_trace_sequential_polarized on host memory (added within
+ * v3): the kernels' per-ray polarization code (csrc/ort_polar.h) inside the host trace, so
+ * the ray geometry is ort_host_trace_pupil's / ort_host_trace_sequential's bit for bit.
+ * pol->coatings and pol->p_out are host pointers; rec: [n_rec][8][n_rays] or NULL. Same
+ * argument checks as the device entry points. */
+int ort_host_trace_pupil_polarized(const ort_lens* lens, const double* px, const double* py,
+                                   ort_rays* rays_out, const ort_batch* batch,
+                                   const ort_options* opt, double* rec, int32_t* updates,
+                                   int32_t* status, const ort_polarization* pol);
+int ort_host_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in,
+                                        ort_rays* rays_out, const ort_batch* batch,
+                                        const ort_options* opt, double* rec, int32_t* updates,
+                                        int32_t* status, const ort_polarization* pol);
+
+/* ort_generate_rays on host memory (added within v3): the rays ort_host_trace_pupil
+ * generates, without a trace (NULL fields of rays_out are skipped). */
+int ort_host_generate_rays(const double* px, const double* py, ort_rays* rays_out,
+                           const ort_batch* batch);
+
 /* threads used by the calls (OpenMP; <= 0: the OpenMP default) */
 void ort_host_set_threads(int32_t n);
 

@@ -970,6 +970,62 @@ int ort_irradiance_bin_vjp(const double* x, const double* y, const double* power
 int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,
                       const ort_batch* batch, void* stream);
 
+/* Coatings and polarized ray tracing (coatings.py, jones.py:56-117,
+ * rays/polarized_rays.py; added within v21: new structs and entry points only).
+ *
+ * Each ray carries the 3x3 complex polarization matrix P (identity at the start). At every
+ * traced surface, after the refraction / reflection, in the surface's local frame, with k0
+ * the direction before and k1 after the interaction:
+ *   s = k0 x k1 (exactly zero: k0 x (1, 0, 0)), normalised; p0 = k0 x s; p1 = k1 x s;
+ *   P <- s (js s^T P) + p1 (jp p0^T P) + k1 (jk k0^T P)
+ * with (js, jp, jk) = (1, 1, 1) without a coating and the Fresnel coefficients of the
+ * coating's own two materials at cos(aoi) = min(|n . k0|, 1) for ORT_COAT_FRESNEL (real
+ * indices only; the root of n^2 - sin^2 is complex when negative). ORT_COAT_SIMPLE
+ * multiplies the intensity by the transmittance (reflective surface: the reflectance) and
+ * leaves P unchanged at that surface, as the reference does. */
+enum ort_coating_kind { ORT_COAT_NONE = 0, ORT_COAT_SIMPLE = 1, ORT_COAT_FRESNEL = 2 };
+typedef struct ort_coating {        /* one per traced surface */
+  int32_t kind;                     /* ort_coating_kind */
+  int32_t mat_pre, mat_post;        /* FRESNEL: columns of n_tab (the coating's own materials) */
+  int32_t reserved;
+  double transmittance, reflectance;
+} ort_coating; /* 32 bytes */
+
+enum ort_polarization_mode {
+  ORT_POL_IGNORE = 0,      /* coatings act on the intensity only; P is not carried to i     */
+  ORT_POL_MATRICES = 1,    /* P is carried, the intensity is left as traced (trace_generic)  */
+  ORT_POL_POLARIZED = 2,   /* i = sum |P E0|^2 (replaces the traced intensity)               */
+  ORT_POL_UNPOLARIZED = 3  /* i = (sum |P E0x|^2 + sum |P E0y|^2) i_initial / 2              */
+};
+typedef struct ort_polarization {
+  int32_t mode;                       /* ort_polarization_mode */
+  int32_t reserved;
+  double ex_re, ex_im, ey_re, ey_im;  /* Ex e^{i phase_x}, Ey e^{i phase_y}, formed on the host */
+  const ort_coating* coatings;        /* device, [n_surfaces] */
+  double* p_out;                      /* device, [18][n_rays] or NULL: plane 2 (3 r + c) is
+                                         Re P[r][c], plane 2 (3 r + c) + 1 its imaginary part */
+} ort_polarization; /* 56 bytes */
+
+/* ort_trace_pupil / ort_trace_sequential with polarization: the same arguments plus `pol`
+ * (required, with pol->coatings). The rays are traced by the trace_kernel<F_POL> family
+ * (every Newton kind compiled in) through the same schedule / verify protocol; their
+ * geometry (x .. N, opd) is the unpolarized trace's, operation for operation. E0 is built
+ * from the ray's initial direction k (generated, or as loaded by the sequential entry):
+ * p = k x (1, 0, 0) normalised, s = p x k, E0 = ex s + ey p (k along x: NaN intensity).
+ * The sequential entry starts P from the identity (no continuation of an earlier P).
+ * ORT_ERR_ARG: per-ray wavelengths (batch->w), a tape or rms request, lenses with
+ * thin-lens, phase, grating or NURBS surfaces. (Verify rounds launch one workgroup per 256
+ * rays: this family has no grid-stride form.) */
+int ort_trace_pupil_polarized(const ort_lens* lens, const double* px, const double* py,
+                              ort_rays* rays_out, const ort_batch* batch,
+                              const ort_options* opt, double* rec, ort_newton_stat* newton_stat,
+                              int32_t* status, const ort_polarization* pol, void* stream);
+int ort_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in,
+                                   ort_rays* rays_out, const ort_batch* batch,
+                                   const ort_options* opt, double* rec,
+                                   ort_newton_stat* newton_stat, int32_t* status,
+                                   const ort_polarization* pol, void* stream);
+
 /* Error codes */
 enum ort_error {
   ORT_OK = 0,

@@ -189,6 +189,28 @@ APODIZATION = np.dtype(
 )
 assert APODIZATION.itemsize == 40
 
+# enum ort_coating_kind / struct ort_coating (one per traced surface; ort_polarization)
+COAT_NONE = 0
+COAT_SIMPLE = 1
+COAT_FRESNEL = 2
+COATING = np.dtype(
+    [
+        ("kind", "<i4"),
+        ("mat_pre", "<i4"),
+        ("mat_post", "<i4"),
+        ("reserved", "<i4"),
+        ("transmittance", "<f8"),
+        ("reflectance", "<f8"),
+    ],
+    align=True,
+)
+assert COATING.itemsize == 32
+# enum ort_polarization_mode
+POL_IGNORE = 0
+POL_MATRICES = 1
+POL_POLARIZED = 2
+POL_UNPOLARIZED = 3
+
 # enum ort_material_kind
 MAT_IDEAL = 0
 MAT_TABULATED = 10

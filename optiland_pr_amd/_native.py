@@ -130,6 +130,19 @@ class ort_options(C.Structure):
     ]
 
 
+class ort_polarization(C.Structure):  # added within v21 (ort_trace_*_polarized)
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("reserved", C.c_int32),
+        ("ex_re", C.c_double),
+        ("ex_im", C.c_double),
+        ("ey_re", C.c_double),
+        ("ey_im", C.c_double),
+        ("coatings", C.c_void_p),
+        ("p_out", C.c_void_p),
+    ]
+
+
 class ort_spot_layout(C.Structure):
     _fields_ = [
         ("n_pupil", C.c_int64),
@@ -157,7 +170,8 @@ EXPORTS = ("ort_abi_version", "ort_trace_sequential", "ort_trace_pupil", "ort_tr
            "ort_patch_zernike_ptrs", "ort_newton_finish", "ort_adam_patch_zernike",
            "ort_rms_finish", "ort_newton_finish_rms", "ort_huygens_workspace_size",
            "ort_huygens_psf", "ort_irradiance_workspace_size", "ort_irradiance_bin",
-           "ort_irradiance_bin_vjp")
+           "ort_irradiance_bin_vjp", "ort_trace_pupil_polarized",
+           "ort_trace_sequential_polarized")
 
 _lib = None
 
@@ -288,6 +302,16 @@ def load(path: str | None = None):
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+    lib.ort_trace_pupil_polarized.restype = C.c_int
+    lib.ort_trace_pupil_polarized.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_rays),
+                                              P(ort_batch), P(ort_options), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, P(ort_polarization),
+                                              C.c_void_p]
+    lib.ort_trace_sequential_polarized.restype = C.c_int
+    lib.ort_trace_sequential_polarized.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays),
+                                                   P(ort_batch), P(ort_options), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, P(ort_polarization),
+                                                   C.c_void_p]
     v = lib.ort_abi_version()
     if v != _abi.ABI_VERSION:
         raise NativeLibraryError(f"ABI version mismatch: library {v}, host {_abi.ABI_VERSION}")
@@ -300,7 +324,8 @@ HOST_EXPORTS = ("ort_host_abi_version", "ort_host_trace_sequential",
                 "ort_host_trace_sequential_vjp", "ort_host_trace_pupil", "ort_host_trace_pupil_vjp",
                 "ort_host_rms_spot", "ort_host_rms_spot_vjp", "ort_host_set_threads",
                 "ort_host_huygens_psf", "ort_host_irradiance_bin",
-                "ort_host_irradiance_bin_vjp")
+                "ort_host_irradiance_bin_vjp", "ort_host_trace_pupil_polarized",
+                "ort_host_trace_sequential_polarized", "ort_host_generate_rays")
 HOST_ABI_VERSION = 3  # include/optiland_host.h ORT_HOST_ABI_VERSION
 
 _host = None
@@ -357,6 +382,18 @@ def load_host(path: str | None = None):
                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]
+    lib.ort_host_trace_pupil_polarized.restype = C.c_int
+    lib.ort_host_trace_pupil_polarized.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p,
+                                                   P(ort_rays), P(ort_batch), P(ort_options),
+                                                   C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   P(ort_polarization)]
+    lib.ort_host_trace_sequential_polarized.restype = C.c_int
+    lib.ort_host_trace_sequential_polarized.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays),
+                                                        P(ort_batch), P(ort_options), C.c_void_p,
+                                                        C.c_void_p, C.c_void_p,
+                                                        P(ort_polarization)]
+    lib.ort_host_generate_rays.restype = C.c_int
+    lib.ort_host_generate_rays.argtypes = [C.c_void_p, C.c_void_p, P(ort_rays), P(ort_batch)]
     v = lib.ort_host_abi_version()
     if v != HOST_ABI_VERSION:
         raise NativeLibraryError(f"host ABI version mismatch: library {v}, host {HOST_ABI_VERSION}")

@@ -36,8 +36,10 @@ int launch_geom(const ort_lens* lens, int32_t surface, int64_t n, const ort_rays
 
 int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
   if (a_in.n_rays == 0) return ORT_OK;
-  const bool closed = (feat & F_IA) == 0 && (feat & F_KM) == 0;
-  KernelFn fn = (feat & F_IA) != 0 ? select_trace_ia(feat & ~F_AXIAL)
+  const bool pol = (feat & F_POL) != 0;  // coated / polarized: always its own family
+  const bool closed = !pol && (feat & F_IA) == 0 && (feat & F_KM) == 0;
+  KernelFn fn = pol                ? select_trace_pol(feat)
+                : (feat & F_IA) != 0 ? select_trace_ia(feat & ~F_AXIAL)
                 : closed           ? select_closed(feat)
                                    : select_trace(feat & ~F_AXIAL);
   if (!fn) return ORT_ERR_ARG;
@@ -47,7 +49,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
                                         : (a_in.n_rays + bs - 1) / bs;
   // a verify-and-re-trace round (statistics to check, or a run_if flag) of a kernel with a
   // grid-stride form (F_STRIDE): at most kVerifyGrid workgroups
-  if (!closed && (feat & F_IA) == 0 && (a_in.vstats || a_in.run_if) && blocks > kVerifyGrid) {
+  if (!closed && !pol && (feat & F_IA) == 0 && (a_in.vstats || a_in.run_if) && blocks > kVerifyGrid) {
     if (KernelFn fs = select_trace((feat | F_STRIDE) & ~F_AXIAL)) {
       fn = fs;
       blocks = kVerifyGrid;
@@ -57,7 +59,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
   KArgs a = a_in;
   // Newton kernels on generated rays whose segments share one pupil: chunk-major block
   // order (pair_major_ray), where it is a bijection over whole blocks
-  a.block_remap = (feat & F_KM) != 0 && (feat & F_IA) == 0 && (feat & F_GEN) != 0 &&
+  a.block_remap = !pol && (feat & F_KM) != 0 && (feat & F_IA) == 0 && (feat & F_GEN) != 0 &&
                   !a.pupil_per_ray && a.seg && a.n_seg > 1 && a.seg_len % kBlock == 0 &&
                   a.n_rays == (int64_t)a.n_seg * a.seg_len;
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(bs), 0, stream, a);
@@ -123,6 +125,34 @@ int ort_trace_pupil(const ort_lens* lens, const double* px, const double* py,
                           nullptr);
 }
 
+int ort_trace_pupil_polarized(const ort_lens* lens, const double* px, const double* py,
+                              ort_rays* rays_out, const ort_batch* batch,
+                              const ort_options* opt, double* rec, ort_newton_stat* newton_stat,
+                              int32_t* status, const ort_polarization* pol, void* stream) {
+  if (!pol) return ORT_ERR_ARG;
+  return trace_pupil_impl(lens, px, py, rays_out, batch, opt, rec, newton_stat, status, stream,
+                          nullptr, pol);
+}
+
+int ort_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in,
+                                   ort_rays* rays_out, const ort_batch* batch,
+                                   const ort_options* opt, double* rec,
+                                   ort_newton_stat* newton_stat, int32_t* status,
+                                   const ort_polarization* pol, void* stream) {
+  if (!rays_in || !rays_out || !batch || !pol) return ORT_ERR_ARG;
+  if (batch->n_rays == 0) return ORT_OK;
+  KArgs a{};
+  uint32_t feat = 0;
+  int rc = fill_args(a, lens, batch, opt, rec, newton_stat, status, feat);
+  if (rc) return rc;
+  if ((rc = fill_pol(a, batch, opt, pol, feat))) return rc;
+  a.in = *rays_in;
+  a.out = *rays_out;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = init_outputs(a, s))) return rc;
+  return launch(a, feat, s);
+}
+
 }  // extern "C"
 
 namespace ortk {
@@ -130,7 +160,7 @@ namespace ortk {
 int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
                      ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
                      double* rec, ort_newton_stat* newton_stat, int32_t* status, void* stream,
-                     SpotFuse* fuse) {
+                     SpotFuse* fuse, const ort_polarization* pol) {
   if (fuse) fuse->fused = false;
   if (!rays_out || !batch) return ORT_ERR_ARG;
   if (batch->n_rays == 0) return ORT_OK;
@@ -143,6 +173,10 @@ int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
   a.py = py;
   a.out = *rays_out;
   feat |= F_GEN;
+  if (pol) {  // ort_trace_pupil_polarized
+    if (fuse) return ORT_ERR_ARG;
+    if ((rc = fill_pol(a, batch, opt, pol, feat))) return rc;
+  }
   if (opt->tape) {  // the adjoint tape of a differentiable trace (Newton lenses)
     if ((feat & F_KM) == 0 || (feat & (F_REC | F_IA | F_WRAY)) != 0 ||
         opt->newton_mode != ORT_NEWTON_SCHEDULE || opt->start_surface != 0)

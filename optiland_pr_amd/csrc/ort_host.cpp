@@ -95,6 +95,7 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
   std::vector<int> lam(n, 0);
   std::vector<double> wl(n, 0.0), t(n), f, nx, ny, nz;
   std::vector<char> unnorm(n, 0);
+  std::vector<ort::PolState> pol(a.coat ? n : 0);  // ort_host_trace_*_polarized
 #pragma omp parallel for num_threads(nt) schedule(static)
   for (int64_t k = 0; k < n; ++k) {
     const int64_t r = r0 + k;
@@ -110,6 +111,7 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
     q.i = a.in.i[r];
     q.opd = a.in.opd[r];
     q.att = 0.0;
+    if (a.coat) ort::pol_init(pol[k], q.L, q.M, q.N, q.i);
   }
   for (int si = a.start_surface; si < a.n_surf; ++si) {
     const ort_surface s = a.surf[si];
@@ -204,7 +206,29 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, a.coef + s.ap_off, s.ap_len);
       bool un = false;
-      interact(a, s, r, o, lam[k], wl[k], un);
+      if (a.coat) {
+        // trace_kernel<F_POL>'s step (refractive / reflective surfaces only): interact()'s
+        // operations on the ray, the normal and the incoming direction kept
+        double ux, uy, uz;
+        ort::surface_normal<kAllKinds>(s, s.radius, s.conic, a.coef, a.zern, kNoSeed, r, ux, uy,
+                                       uz);
+        const double k0x = r.L, k0y = r.M, k0z = r.N;
+        const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
+        if (refl)
+          ort::reflect(r, ux, uy, uz);
+        else
+          ort::refract(r, ux, uy, uz, o.u);
+        const ort_coating ct = a.coat[si];
+        double n1 = 1.0, n2 = 1.0;
+        if (ct.kind == ORT_COAT_FRESNEL) {
+          n1 = tab(a.n_tab, a.n_lambda, a.n_mat, lam[k], ct.mat_pre);
+          n2 = tab(a.n_tab, a.n_lambda, a.n_mat, lam[k], ct.mat_post);
+        }
+        ort::pol_surface(pol[k], ct, refl, ux, uy, uz, k0x, k0y, k0z, r.L, r.M, r.N, n1, n2,
+                         r.i);
+      } else {
+        interact(a, s, r, o, lam[k], wl[k], un);
+      }
       if (un) unnorm[k] = 1;
       globalize(a, s, r);
       if (a.rec && (s.flags & ORT_SURF_RECORD)) {
@@ -240,6 +264,15 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
     a.out.N[q] = r.N;
     a.out.i[q] = ort::intensity(r);
     a.out.opd[q] = r.opd;
+    if (a.coat) {
+      a.out.i[q] = ort::pol_intensity(pol[k], a.pol_mode, a.pol_ex, a.pol_ey, ort::intensity(r));
+      if (a.p_out) {
+        for (int e = 0; e < 9; ++e) {
+          a.p_out[(int64_t)(2 * e) * a.n_rays + q] = pol[k].re[e];
+          a.p_out[(int64_t)(2 * e + 1) * a.n_rays + q] = pol[k].im[e];
+        }
+      }
+    }
   }
 }
 
@@ -296,6 +329,20 @@ void vjp_chunks(const KArgs& a, const JArgs& j, std::vector<double>& part, int64
 
 }  // namespace
 
+// every Newton group of the batch through trace_group (updates: [n_groups][n_surfaces])
+static int trace_groups(const KArgs& a, int32_t* updates, int32_t* status, int st) {
+  const int64_t n_groups = (a.n_rays + a.group_len - 1) / a.group_len;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    const int64_t r0 = g * a.group_len, r1 = std::min(a.n_rays, r0 + a.group_len);
+    int32_t* up = updates ? updates + g * a.n_surf : nullptr;
+    if (up)
+      for (int s = 0; s < a.n_surf; ++s) up[s] = 0;
+    trace_group(a, r0, r1, up, st);
+  }
+  if (status) *status = st;
+  return ORT_OK;
+}
+
 // sum of term(k), lo <= k < hi: halves down to runs of at most 8 terms added in order
 template <class F>
 static double pairwise_sum(int64_t lo, int64_t hi, const F& term) {
@@ -314,10 +361,12 @@ int ort_host_abi_version(void) { return ORT_HOST_ABI_VERSION; }
 
 void ort_host_set_threads(int32_t n) { g_threads = n; }
 
-int ort_host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
-                              ort_rays* rays_out, const ort_batch* batch,
-                              const ort_options* opt, double* rec, int32_t* updates,
-                              int32_t* status) {
+// shared body of ort_host_trace_sequential and its polarized form (pol: NULL or the
+// coatings / mode of ort_host_trace_sequential_polarized)
+static int host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
+                                 ort_rays* rays_out, const ort_batch* batch,
+                                 const ort_options* opt, double* rec, int32_t* updates,
+                                 int32_t* status, const ort_polarization* pol) {
   if (!rays_in || !rays_out || !batch) return ORT_ERR_ARG;
   const ort_options dflt{ORT_NEWTON_SCHEDULE, 0, nullptr, 0, 0};
   if (!opt) opt = &dflt;
@@ -326,21 +375,28 @@ int ort_host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
   uint32_t feat = 0;
   int rc = fill_args(a, lens, batch, opt, rec, nullptr, status, feat);
   if (rc) return rc;
+  if (pol && (rc = fill_pol(a, batch, opt, pol, feat))) return rc;
   a.in = *rays_in;
   a.out = *rays_out;
   if (status) *status = 0;
   if (a.n_rays == 0) return ORT_OK;
-  const int64_t n_groups = (a.n_rays + a.group_len - 1) / a.group_len;
-  int st = 0;
-  for (int64_t g = 0; g < n_groups; ++g) {
-    const int64_t r0 = g * a.group_len, r1 = std::min(a.n_rays, r0 + a.group_len);
-    int32_t* up = updates ? updates + g * a.n_surf : nullptr;
-    if (up)
-      for (int s = 0; s < a.n_surf; ++s) up[s] = 0;
-    trace_group(a, r0, r1, up, st);
-  }
-  if (status) *status = st;
-  return ORT_OK;
+  return trace_groups(a, updates, status, 0);
+}
+
+int ort_host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
+                              ort_rays* rays_out, const ort_batch* batch,
+                              const ort_options* opt, double* rec, int32_t* updates,
+                              int32_t* status) {
+  return host_trace_sequential(lens, rays_in, rays_out, batch, opt, rec, updates, status,
+                               nullptr);
+}
+
+int ort_host_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in,
+                                        ort_rays* rays_out, const ort_batch* batch,
+                                        const ort_options* opt, double* rec, int32_t* updates,
+                                        int32_t* status, const ort_polarization* pol) {
+  if (!pol) return ORT_ERR_ARG;
+  return host_trace_sequential(lens, rays_in, rays_out, batch, opt, rec, updates, status, pol);
 }
 
 }  // extern "C"
@@ -494,9 +550,11 @@ int ort_host_trace_sequential_vjp(const ort_lens* lens, const ort_rays* rays_in,
   return host_vjp<true>(a, lens, params, cotangent, rec_cotangent, rec, grad, grad_in, want_in);
 }
 
-int ort_host_trace_pupil(const ort_lens* lens, const double* px, const double* py,
-                         ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
-                         int32_t* updates, int32_t* status) {
+// shared body of ort_host_trace_pupil and its polarized form
+static int host_trace_pupil(const ort_lens* lens, const double* px, const double* py,
+                            ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
+                            double* rec, int32_t* updates, int32_t* status,
+                            const ort_polarization* pol) {
   if (!px || !py || !rays_out || !batch || !batch->seg || batch->n_seg < 1 || batch->w)
     return ORT_ERR_ARG;
   const ort_options dflt{ORT_NEWTON_SCHEDULE, 0, nullptr, 0, 0};
@@ -504,8 +562,9 @@ int ort_host_trace_pupil(const ort_lens* lens, const double* px, const double* p
   if (opt->tape || opt->verify_stats || opt->run_if || opt->start_surface) return ORT_ERR_ARG;
   KArgs a{};
   uint32_t feat = 0;
-  int rc = fill_args(a, lens, batch, opt, nullptr, nullptr, status, feat);
+  int rc = fill_args(a, lens, batch, opt, rec, nullptr, status, feat);
   if (rc) return rc;
+  if (pol && (rc = fill_pol(a, batch, opt, pol, feat))) return rc;
   if (batch->n_rays != (int64_t)batch->n_seg * batch->seg_len) return ORT_ERR_ARG;
   a.out = *rays_out;
   if (status) *status = 0;
@@ -514,17 +573,44 @@ int ort_host_trace_pupil(const ort_lens* lens, const double* px, const double* p
   ort_rays gen;
   generate_host(a, px, py, buf, gen);
   a.in = gen;
-  const int64_t n_groups = (a.n_rays + a.group_len - 1) / a.group_len;
   int st = 0;
   if (a.apod && (uint32_t)a.apod->kind > (uint32_t)ORT_APOD_TUKEY) st |= ORT_STATUS_BAD_APODIZATION;
-  for (int64_t g = 0; g < n_groups; ++g) {
-    const int64_t r0 = g * a.group_len, r1 = std::min(a.n_rays, r0 + a.group_len);
-    int32_t* up = updates ? updates + g * a.n_surf : nullptr;
-    if (up)
-      for (int s = 0; s < a.n_surf; ++s) up[s] = 0;
-    trace_group(a, r0, r1, up, st);
-  }
-  if (status) *status = st;
+  return trace_groups(a, updates, status, st);
+}
+
+int ort_host_trace_pupil(const ort_lens* lens, const double* px, const double* py,
+                         ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
+                         int32_t* updates, int32_t* status) {
+  return host_trace_pupil(lens, px, py, rays_out, batch, opt, nullptr, updates, status, nullptr);
+}
+
+int ort_host_trace_pupil_polarized(const ort_lens* lens, const double* px, const double* py,
+                                   ort_rays* rays_out, const ort_batch* batch,
+                                   const ort_options* opt, double* rec, int32_t* updates,
+                                   int32_t* status, const ort_polarization* pol) {
+  if (!pol) return ORT_ERR_ARG;
+  return host_trace_pupil(lens, px, py, rays_out, batch, opt, rec, updates, status, pol);
+}
+
+int ort_host_generate_rays(const double* px, const double* py, ort_rays* rays_out,
+                           const ort_batch* batch) {
+  if (!rays_out || !batch) return ORT_ERR_ARG;
+  if (batch->n_rays == 0) return ORT_OK;
+  if (!px || !py || !batch->seg || batch->seg_len < 1 || batch->n_rays < 0) return ORT_ERR_ARG;
+  KArgs a{};
+  a.n_rays = batch->n_rays;
+  a.seg_len = batch->seg_len;
+  a.seg = batch->seg;
+  a.pupil_per_ray = batch->pupil_per_ray;
+  a.apod = batch->apod;
+  std::vector<double> buf;
+  ort_rays gen;
+  generate_host(a, px, py, buf, gen);
+  const double* src[8] = {gen.x, gen.y, gen.z, gen.L, gen.M, gen.N, gen.i, gen.opd};
+  double* dst[8] = {rays_out->x, rays_out->y, rays_out->z, rays_out->L,
+                    rays_out->M, rays_out->N, rays_out->i, rays_out->opd};
+  for (int k = 0; k < 8; ++k)
+    if (dst[k]) std::copy(src[k], src[k] + a.n_rays, dst[k]);
   return ORT_OK;
 }
 

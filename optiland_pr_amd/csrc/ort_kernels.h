@@ -74,7 +74,7 @@ struct SpotFuse {
 int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
                      ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
                      double* rec, ort_newton_stat* newton_stat, int32_t* status, void* stream,
-                     SpotFuse* fuse);
+                     SpotFuse* fuse, const ort_polarization* pol = nullptr);
 
 // the F_SPOT epilogue (ort_reduce.h): every thread of the block calls it
 template <uint32_t FEAT>
@@ -519,16 +519,21 @@ constexpr bool kNewtonFast =
     false;
 #else
     (FEAT & F_KM) != 0 && (FEAT & F_KM & ~(ort::KM_EVEN | ort::KM_ODD)) == 0 &&
-    (FEAT & (F_IA | F_WRAY | F_TAPE)) == 0;
+    (FEAT & (F_IA | F_WRAY | F_TAPE | F_POL)) == 0;
 #endif
 
 // The verify rounds' grid-stride form (F_STRIDE) usually returns at once and re-traces
 // only after a schedule correction: 2 waves per SIMD, so it carries no scratch (its
 // dispatch sets up no spill space).
+// trace_kernel<F_POL> (ort_k_trace_pol.hip) carries 22 more doubles per lane (the
+// polarization matrix, the initial direction and intensity) on top of the all-kinds Newton
+// kernel: see DESIGN.md section 12 for the compiler's figures behind this choice.
+constexpr int kPolWaves = 2;
 template <uint32_t FEAT>
 struct TraceWaves {
   static constexpr int value =
       (FEAT & F_STRIDE) != 0 ? 2
+      : (FEAT & F_POL) != 0 ? kPolWaves
       : ((FEAT & ort::KM_ZERN) != 0 && (FEAT & (ort::KM_FREE | F_IA)) == 0)
           ? ((FEAT & F_TAPE) != 0 ? 4 : 6)
           : ((kNewtonFast<FEAT> && (FEAT & F_MONO) != 0) ? 5 : 1);
@@ -915,6 +920,8 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
     if (a.apod && (uint32_t)cst(a.apod)->kind > (uint32_t)ORT_APOD_TUKEY)
       range_bits |= ORT_STATUS_BAD_APODIZATION;
   }
+  ort::PolState pol;  // F_POL: P = identity, the initial direction and intensity
+  if constexpr ((FEAT & F_POL) != 0) pol_init(pol, r.L, r.M, r.N, r.i);
 
   for (int si = a.start_surface; si < a.n_surf; ++si) {
     const ort_surface s = cst(a.surf)[si];
@@ -956,6 +963,27 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
       interact<FEAT>(a, s, r, o, lam, wl, unnorm);
+    } else if constexpr ((FEAT & F_POL) != 0) {
+      // the generic step below with the normal and the direction before the interaction
+      // kept for the polarization update (the ray's own operations are unchanged)
+      to_intersection(a, s, r, t, alpha, n_pre);
+      double nx = hnx, ny = hny, nz = hnz;
+      if (!hn)
+        ort::surface_normal<(FEAT & F_KM)>(s, s.radius, s.conic, cst(a.coef), cst(a.zern),
+                                           kNoSeed, r, nx, ny, nz);
+      const double k0x = r.L, k0y = r.M, k0z = r.N;
+      const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
+      if (refl)
+        ort::reflect(r, nx, ny, nz);
+      else
+        ort::refract(r, nx, ny, nz, u);
+      const ort_coating ct = cst(a.coat)[si];
+      double n1 = 1.0, n2 = 1.0;  // the coating's own materials at this wavelength
+      if (ct.kind == ORT_COAT_FRESNEL) {
+        n1 = tab(a.n_tab, a.n_lambda, a.n_mat, lam, ct.mat_pre);
+        n2 = tab(a.n_tab, a.n_lambda, a.n_mat, lam, ct.mat_post);
+      }
+      ort::pol_surface(pol, ct, refl, nx, ny, nz, k0x, k0y, k0z, r.L, r.M, r.N, n1, n2, r.i);
     } else if constexpr ((FEAT & F_KM) != 0) {
       if (hn) {  // finish_surface with the normal of the last Newton evaluation
         to_intersection(a, s, r, t, alpha, n_pre);
@@ -1000,6 +1028,19 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
   if (range_bits && active && a.status) atomicOr(a.status, range_bits);
   if constexpr ((FEAT & F_RMS) != 0) rms_epilogue(a, r, active, vb);
   if (!active) return;
+  if constexpr ((FEAT & F_POL) != 0) {
+    // PolarizedRays.update_intensity per the mode, and the optional planes of P
+    const double inten = ort::pol_intensity(pol, a.pol_mode, a.pol_ex, a.pol_ey, ort::intensity(r));
+    store_ray(a, rid, r, &inten);
+    if (a.p_out) {
+#pragma unroll
+      for (int e = 0; e < 9; ++e) {
+        ORT_ST(a.p_out[(int64_t)(2 * e) * a.n_rays + rid], pol.re[e]);
+        ORT_ST(a.p_out[(int64_t)(2 * e + 1) * a.n_rays + rid], pol.im[e]);
+      }
+    }
+    return;
+  }
   store_ray(a, rid, r);
 }
 
@@ -1472,6 +1513,7 @@ KernelFn select_trace_mono(uint32_t feat); // Newton lenses, F_GEN, wave-uniform
                                            // (ort_k_trace_mono.hip)
 KernelFn select_trace_ia(uint32_t feat);   // thin-lens / phase / grating lenses (ort_k_trace_ia.hip)
 KernelFn select_trace_tape(uint32_t feat); // Newton lenses, F_GEN, writing the adjoint tape
+KernelFn select_trace_pol(uint32_t feat);  // coated / polarized lenses          (ort_k_trace_pol.hip)
                                            // (ort_k_trace_tape.hip)
 // n(w), k(w) of one material (ort_material_nk)                            (ort_k_closed.hip)
 void launch_material_nk(const ort_material* mats, const double* coef, int32_t mat,

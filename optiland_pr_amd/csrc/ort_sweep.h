@@ -23,6 +23,7 @@
 #include "ort_core.h"
 #include "ort_interact.h"
 #include "ort_material.h"
+#include "ort_polar.h"
 
 namespace ortk {
 
@@ -61,6 +62,8 @@ enum : uint32_t {
                      // epilogue (ort_options.rms_part)
   F_STRIDE = 1u << 13,  // Newton kernel of a verify-and-re-trace round: a grid of at most
                         // kVerifyGrid workgroups strides over the blocks of rays
+  F_POL = 1u << 14,  // coatings / the polarization matrix per ray (ort_polar.h,
+                     // ort_trace_*_polarized)
 };
 
 // Adjoint tape (adj_ray): per surface, rows of n_rays doubles -- the incoming global
@@ -146,7 +149,30 @@ struct KArgs {
   int32_t spot_n_ops;
   int32_t spot_chunks;
   double* rms_part;  // F_RMS: [workgroup][4] (ort_options.rms_part)
+  // F_POL (ort_polarization): the surfaces' coatings, the intensity mode with the input
+  // field (ex, ey) and the optional [18][n_rays] planes of P
+  const ort_coating* coat;
+  int32_t pol_mode;
+  ort::Cplx pol_ex, pol_ey;
+  double* p_out;
 };
+
+// ort_trace_*_polarized: the checks beyond fill_args and the F_POL arguments. Lenses with
+// thin-lens / phase / grating surfaces (and NURBS lenses, which ride on F_IA), per-ray
+// wavelengths, a tape or an rms request are refused.
+inline int fill_pol(KArgs& a, const ort_batch* batch, const ort_options* opt,
+                    const ort_polarization* pol, uint32_t& feat) {
+  if (!pol || !pol->coatings || batch->w || opt->tape || opt->rms_part) return ORT_ERR_ARG;
+  if (pol->mode < ORT_POL_IGNORE || pol->mode > ORT_POL_UNPOLARIZED) return ORT_ERR_ARG;
+  if (feat & (F_IA | F_WRAY | ort::KM_NURBS)) return ORT_ERR_ARG;
+  a.coat = pol->coatings;
+  a.pol_mode = pol->mode;
+  a.pol_ex = {pol->ex_re, pol->ex_im};
+  a.pol_ey = {pol->ey_re, pol->ey_im};
+  a.p_out = pol->p_out;
+  feat |= F_POL;
+  return ORT_OK;
+}
 
 // KArgs from the C ABI structs (argument checks included) and the kernel feature bits the
 // lens and batch call for (F_KM kinds, F_REC, F_WRAY / F_MONO, F_IA, F_AXIAL).

@@ -127,7 +127,8 @@ class RadialPhaseProfile(BasePhaseProfile):
 # interaction models (optiland/interactions)
 # --------------------------------------------------------------------------------------
 class BaseInteractionModel:
-    """interactions/base.py:24-128 (coatings and BSDFs are out of scope)."""
+    """interactions/base.py:24-128 (BSDF scattering is out of scope; a coating is applied
+    by the trace kernels, csrc/ort_polar.h)."""
 
     interaction_id = _abi.IA_REFRACT_REFLECT
     _registry: dict = {}
@@ -137,11 +138,16 @@ class BaseInteractionModel:
         BaseInteractionModel._registry[cls.__name__] = cls
 
     def __init__(self, parent_surface=None, is_reflective=False, coating=None, bsdf=None):
-        if coating is not None or bsdf is not None:
-            raise ValueError("coatings and BSDF scattering are out of scope for the trace core")
+        if bsdf is not None:
+            raise ValueError("BSDF scattering is out of scope for the trace core")
+        if coating is not None:
+            from .polarization import BaseCoating
+
+            if not isinstance(coating, BaseCoating):
+                raise ValueError("coating must be a BaseCoating (polarization.py)")
         self.parent_surface = parent_surface
         self.is_reflective = bool(is_reflective)
-        self.coating = None
+        self.coating = coating
         self.bsdf = None
 
     def flip(self):
@@ -149,7 +155,7 @@ class BaseInteractionModel:
 
     def to_dict(self):
         return {"type": type(self).__name__, "is_reflective": self.is_reflective,
-                "coating": None, "bsdf": None}
+                "coating": self.coating.to_dict() if self.coating else None, "bsdf": None}
 
     @classmethod
     def from_dict(cls, data, parent_surface=None):
@@ -157,10 +163,13 @@ class BaseInteractionModel:
         if sub is None:
             raise ValueError(f"Unknown interaction model type: {data.get('type')}")
         kw = {k: v for k, v in data.items() if k not in ("type", "material_pre")}
-        if kw.get("coating") or kw.get("bsdf"):
-            raise ValueError("coatings and BSDF scattering are out of scope for the trace core")
-        kw.pop("coating", None)
+        if kw.get("bsdf"):
+            raise ValueError("BSDF scattering is out of scope for the trace core")
         kw.pop("bsdf", None)
+        if kw.get("coating"):
+            kw["coating"] = coating_from_dict(kw["coating"])
+        else:
+            kw.pop("coating", None)
         return sub._from_kwargs(parent_surface, kw)
 
     @classmethod
@@ -170,6 +179,16 @@ class BaseInteractionModel:
     def lower(self, geometry):
         """-> the parameter block in lens.coef (ort_interaction)."""
         return []
+
+
+def coating_from_dict(data):
+    """BaseCoating.from_dict with malformed dictionaries reported as ValueError."""
+    from .polarization import BaseCoating
+
+    try:
+        return BaseCoating.from_dict(data)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"invalid coating dictionary {data!r}: missing or unknown {e}") from e
 
 
 class RefractiveReflectiveModel(BaseInteractionModel):
@@ -241,16 +260,19 @@ class DiffractiveInteractionModel(RefractiveReflectiveModel):
         raise ValueError("the diffractive interaction needs a grating geometry")
 
 
-def make_interaction(interaction_type, is_reflective, focal_length=None, phase_profile=None):
+def make_interaction(interaction_type, is_reflective, focal_length=None, phase_profile=None,
+                     coating=None):
     """surfaces/factories/interaction_model_factory.py:29-90."""
     if interaction_type == "refractive_reflective":
-        return RefractiveReflectiveModel(is_reflective=is_reflective)
+        return RefractiveReflectiveModel(is_reflective=is_reflective, coating=coating)
     if interaction_type == "thin_lens":
-        return ThinLensInteractionModel(focal_length=focal_length, is_reflective=is_reflective)
+        return ThinLensInteractionModel(focal_length=focal_length, is_reflective=is_reflective,
+                                        coating=coating)
     if interaction_type == "diffractive":
-        return DiffractiveInteractionModel(is_reflective=is_reflective)
+        return DiffractiveInteractionModel(is_reflective=is_reflective, coating=coating)
     if interaction_type == "phase":
         if phase_profile is None:
             raise ValueError("phase_profile is required for phase interaction.")
-        return PhaseInteractionModel(phase_profile=phase_profile, is_reflective=is_reflective)
+        return PhaseInteractionModel(phase_profile=phase_profile, is_reflective=is_reflective,
+                                     coating=coating)
     raise ValueError(f"Unknown interaction_type: {interaction_type}")

@@ -40,7 +40,7 @@ from .geometries import (
     ZernikePolynomialGeometry,
     scalar,
 )
-from .interactions import BaseInteractionModel, RefractiveReflectiveModel
+from .interactions import BaseInteractionModel, RefractiveReflectiveModel, coating_from_dict
 from .materials import AbbeMaterial, IdealMaterial, Material
 from .apertures import BaseAperture
 from .surfaces import ObjectSurface, Surface
@@ -256,9 +256,8 @@ def optic_from_dict(data):
     sg = optic.surface_group
     prev = None
     for k, sd in enumerate(data["surface_group"]["surfaces"]):
-        for key in ("coating", "bsdf"):
-            if sd.get(key):
-                raise ValueError(f"surface {k}: {key} is out of scope for the trace core")
+        if sd.get("bsdf"):
+            raise ValueError(f"surface {k}: bsdf is out of scope for the trace core")
         geometry = geometry_from_dict(sd["geometry"])
         post = material_from_dict(sd["material_post"])
         if sd.get("type") == "ObjectSurface" or k == 0:
@@ -273,6 +272,8 @@ def optic_from_dict(data):
             imd = sd.get("interaction_model")  # standard_surface.py:352-365
             model = (BaseInteractionModel.from_dict(imd) if imd else
                      RefractiveReflectiveModel(is_reflective=bool(sd.get("is_reflective", False))))
+            if sd.get("coating"):  # standard_surface.py:359-366: the surface's own entry
+                model.coating = coating_from_dict(sd["coating"])
             s = Surface(prev, post, geometry, is_stop=bool(sd.get("is_stop", False)),
                         aperture=aperture, surface_type=sd.get("surface_type"),
                         interaction_model=model)
@@ -283,7 +284,13 @@ def optic_from_dict(data):
         s.thickness = _f(sd.get("thickness"))
         sg.surfaces.append(s)
         prev = s
+    # linking replaces a surface's coating by the derived Fresnel one (Surface.
+    # previous_surface): the file's coatings are put back as they were written
+    coatings = [s.coating for s in sg.surfaces]
     sg._relink()
+    for s, c in zip(sg.surfaces, coatings, strict=True):
+        if c is not None:
+            s.interaction_model.coating = c
     sg.use_absolute_cs = True
     fields = data.get("fields", {})
     fdef = fields.get("field_definition")
@@ -320,7 +327,8 @@ def optic_to_dict(optic):
         if not isinstance(s, ObjectSurface):
             d.update(material_pre=material_to_dict(s.material_pre), is_stop=bool(s.is_stop),
                      aperture=None if s.aperture is None else s.aperture.to_dict(),
-                     coating=None, bsdf=None, is_reflective=bool(s.is_reflective),
+                     coating=s.coating.to_dict() if s.coating else None, bsdf=None,
+                     is_reflective=bool(s.is_reflective),
                      surface_type=s.surface_type,
                      interaction_model=s.interaction_model.to_dict())
         surfaces.append(d)

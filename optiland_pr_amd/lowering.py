@@ -52,6 +52,9 @@ class LensTable:
     # pupil apodization of generated rays (_abi.APODIZATION record; None: intensity 1).
     # An Optic-level property (optic.py:137): set by raytrace.lens_for from the Optic.
     apod: np.ndarray = None
+    # one _abi.COATING record per traced surface (ort_polarization.coatings); a
+    # FresnelCoating's own materials are columns of n_tab
+    coatings: np.ndarray = None
 
     @property
     def n_surfaces(self):
@@ -117,6 +120,8 @@ class LensTable:
         parts.append(np.array([self.final_thickness], dtype=np.float64).tobytes())
         if self.apod is not None:
             parts.append(np.ascontiguousarray(self.apod).tobytes())
+        if self.coatings is not None and np.any(self.coatings["kind"] != _abi.COAT_NONE):
+            parts.append(np.ascontiguousarray(self.coatings).tobytes())
         return b"".join(parts)
 
 
@@ -172,11 +177,14 @@ def _material_n_alpha(m, w):
     return hit
 
 
-def lower_surface_group(surface_group, wavelengths, record=False, skip_object=True):
+def lower_surface_group(surface_group, wavelengths, record=False, skip_object=True,
+                        polarized=False):
     """Lower every traced surface (index >= 1) of `surface_group`.
 
     record: False, True (all traced surfaces) or an iterable of traced-surface
     indices (0-based within the traced surfaces) to snapshot (standard_surface.py:266-286).
+    polarized: the table is for the coated / polarized trace (ort_trace_*_polarized), which
+    has no thin-lens, phase, grating or NURBS surfaces: those raise ValueError here.
     """
     surfs = [s for s in surface_group.surfaces if not isinstance(s, ObjectSurface)]
     if len(surfs) > _abi.MAX_SURFACES:
@@ -205,6 +213,7 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
     ops, coef, zern = [], [], []
     ap_progs = []
     ia_blocks = []
+    coat_rows = []
     device_coeffs = []
     for si, s in enumerate(surfs):
         g = s.geometry
@@ -283,6 +292,24 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
                 ia_blocks.append((si, [float(v) for v in im.lower(g)]))
         row["mat_pre"] = mat_id(s.material_pre)
         row["mat_post"] = mat_id(s.material_post)
+        coating = getattr(im, "coating", None)
+        if coating is not None:
+            from .polarization import FresnelCoating, SimpleCoating
+
+            if isinstance(coating, FresnelCoating):  # the coating's own materials
+                coat_rows.append((si, _abi.COAT_FRESNEL, mat_id(coating.material_pre),
+                                  mat_id(coating.material_post), 0.0, 0.0))
+            elif isinstance(coating, SimpleCoating):
+                coat_rows.append((si, _abi.COAT_SIMPLE, 0, 0, float(coating.transmittance),
+                                  float(coating.reflectance)))
+            else:
+                raise ValueError(f"coating {type(coating).__name__} is not lowered to the "
+                                 "trace core (supported: SimpleCoating, FresnelCoating)")
+        if polarized and (row.get("interaction", _abi.IA_REFRACT_REFLECT)
+                          != _abi.IA_REFRACT_REFLECT or g.geometry_id == _abi.GEOM_NURBS):
+            raise ValueError(
+                f"surface {si + 1}: thin-lens, phase, grating and NURBS surfaces are not "
+                "supported with coatings or a polarization state")
         loc = g.cs.localize_ops()
         glob = g.cs.globalize_ops()
         # localize starts with translate(-t) of the root frame and globalize ends with
@@ -349,6 +376,9 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
             row["flags"] |= _abi.SURF_ALPHA_ALL
         elif np.all(a == 0):
             row["flags"] |= _abi.SURF_ALPHA_NONE
+    coatings = np.zeros(max(1, len(surfs)), dtype=_abi.COATING)
+    for si, kind, mp, mq, tr, rf in coat_rows:
+        coatings[si] = (kind, mp, mq, 0, tr, rf)
     table = np.zeros(len(surfs), dtype=_abi.SURFACE)
     for name in {k for row in rows for k in row}:
         table[name] = [row.get(name, 0) for row in rows]
@@ -367,6 +397,7 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
         n_rec=len(rec_set),
         rec_surfaces=rec_set,
         device_coeffs=device_coeffs,
+        coatings=coatings,
     )
 
 

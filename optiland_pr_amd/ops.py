@@ -1242,3 +1242,77 @@ def _irradiance_backward(ctx, grad):
 
 
 irradiance_bin.register_autograd(_irradiance_backward, setup_context=_irradiance_setup)
+
+
+# --------------------------------------------------------------------------------------
+# ort::trace_pupil_polarized (coatings / polarization; forward only)
+# --------------------------------------------------------------------------------------
+def polarized_args(lens, segs, px, py, n, seg_len, mode, state, pupil_per_ray=False,
+                   want_p=True):
+    """The arguments of torch.ops.ort.trace_pupil_polarized for a DeviceLens / HostLens of a
+    table lowered with polarized=True: the lens tensors, its COATING records and the
+    SEGMENT / APODIZATION records as uint8 tensors on the lens's device, the pupil, the
+    input field (ex_re, ex_im, ey_re, ey_im) and plan_meta = [n, seg_len, pupil_per_ray,
+    mode, want_p]."""
+    from . import polarization as pz
+
+    L, meta, ft, key = lens_args(lens)
+    dev = lens.device
+    coat = pz._coatings_of(lens)
+    seg = segs if torch.is_tensor(segs) else pz._bytes_tensor(
+        np.asarray(segs, dtype=_abi.SEGMENT)).to(dev)
+    apod = pz._apod_of(lens)
+    ex = ey = 0j
+    if mode == _abi.POL_POLARIZED:
+        ex, ey = state.field()
+    return (L, meta, ft, key, coat, seg, apod, px, py,
+            [ex.real, ex.imag, ey.real, ey.imag],
+            [int(n), int(seg_len), int(bool(pupil_per_ray)), int(mode), int(bool(want_p))])
+
+
+@torch.library.custom_op("ort::trace_pupil_polarized", mutates_args=(), device_types="cuda")
+def trace_pupil_polarized(lens: list[torch.Tensor], lens_meta: list[int],
+                          final_thickness: float, lens_key: int, coatings: torch.Tensor,
+                          seg: torch.Tensor, apod: torch.Tensor | None, px: torch.Tensor,
+                          py: torch.Tensor, field: list[float],
+                          plan_meta: list[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    """Optic.trace's fused generation + trace of a coated / polarized lens
+    (ort_trace_pupil_polarized): the rays [8, n] (x y z L M N i opd, i per the mode) and
+    the planes of the polarization matrices [18, n] ([18, 0] unless plan_meta's want_p).
+    Forward only: a backward through it raises."""
+    from . import polarization as pz
+
+    dl = _resolve(lens, lens_meta, final_thickness, lens_key)
+    n, seg_len, ppr, mode, want_p = plan_meta[:5]
+    rays = torch.empty((8, n), dtype=torch.float64, device=dl.device)
+    planes = torch.empty((18, n if want_p else 0), dtype=torch.float64, device=dl.device)
+    pz.trace_pupil_polarized(
+        dl, seg, px.detach().contiguous(), py.detach().contiguous(), n, seg_len, mode, None,
+        pupil_per_ray=bool(ppr), want_p=bool(want_p),
+        field=(complex(field[0], field[1]), complex(field[2], field[3])), coat=coatings,
+        apod=apod, outs=list(rays.unbind(0)), planes=planes.view(-1) if want_p else None)
+    return rays, planes
+
+
+@trace_pupil_polarized.register_kernel("cpu")
+def _trace_pupil_polarized_cpu(lens, lens_meta, final_thickness, lens_key, coatings, seg, apod,
+                               px, py, field, plan_meta):
+    """The CPU dispatch key: the host build (ort_host_trace_pupil_polarized)."""
+    return trace_pupil_polarized._init_fn(lens, lens_meta, final_thickness, lens_key, coatings,
+                                          seg, apod, px, py, field, plan_meta)
+
+
+@trace_pupil_polarized.register_fake
+def _(lens, lens_meta, final_thickness, lens_key, coatings, seg, apod, px, py, field,
+      plan_meta):
+    n, want_p = plan_meta[0], plan_meta[4]
+    return (px.new_empty((8, n), dtype=torch.float64),
+            px.new_empty((18, n if want_p else 0), dtype=torch.float64))
+
+
+def _polarized_backward(ctx, *grads):
+    raise RuntimeError("ort::trace_pupil_polarized is forward only: autograd through "
+                       "coatings / polarization is not supported")
+
+
+trace_pupil_polarized.register_autograd(_polarized_backward)

@@ -57,6 +57,25 @@ class Optic:
         self._lowered = None
         self.aperture = Aperture(aperture_type, value)
 
+    def set_polarization(self, polarization):
+        """optic.py:390-399 -> optic_updater.py:144-158: a PolarizationState or "ignore"."""
+        if isinstance(polarization, str) and polarization != "ignore":
+            raise ValueError("Invalid polarization state. Must be either "
+                             'PolarizationState or "ignore".')
+        self.polarization = polarization
+
+    @property
+    def polarization_state(self):
+        """optic.py:182-201: the PolarizationState, or None for "ignore"."""
+        from .polarization import PolarizationState
+
+        if self.polarization == "ignore":
+            return None
+        if isinstance(self.polarization, PolarizationState):
+            return self.polarization
+        raise ValueError("Invalid polarization state. Must be either "
+                         'PolarizationState or "ignore".')
+
     def set_apodization(self, apodization=None, **kwargs):
         """optic.py:401-419 -> optic_updater.py:312-350: an apodization instance, a
         class name plus its keyword arguments, a to_dict() dict, or None."""
@@ -159,13 +178,15 @@ class Optic:
 
     # -- tracing ----------------------------------------------------------------------
     def trace(self, Hx, Hy, wavelength, num_rays=100, distribution="hexapolar"):
-        """optic.py:584-609 -> RealRayTracer.trace (HIP)."""
+        """optic.py:584-609 -> RealRayTracer.trace (HIP). With a polarization state set the
+        rays are PolarizedRays whose .i is the state's intensity."""
         from .raytrace import RealRayTracer
 
         return RealRayTracer(self).trace(Hx, Hy, wavelength, num_rays, distribution)
 
     def trace_generic(self, Hx, Hy, Px, Py, wavelength):
-        """optic.py:611-632 -> RealRayTracer.trace_generic (HIP)."""
+        """optic.py:611-632 -> RealRayTracer.trace_generic (HIP); PolarizedRays without the
+        intensity update when a polarization state is set."""
         from .raytrace import RealRayTracer
 
         return RealRayTracer(self).trace_generic(Hx, Hy, Px, Py, wavelength)

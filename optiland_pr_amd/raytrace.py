@@ -344,7 +344,7 @@ class DeviceLens:
         self.sched_cache["_default"] = sched.max(axis=0)
 
 
-def lens_for(optic_or_group, wavelengths, record=False, image_record=False):
+def lens_for(optic_or_group, wavelengths, record=False, image_record=False, polarized=False):
     """Lowered + uploaded lens, cached on the Optic.
 
     The host lowering (~0.3 ms) runs on every call and the cached upload is reused only
@@ -356,6 +356,8 @@ def lens_for(optic_or_group, wavelengths, record=False, image_record=False):
     sg = getattr(host, "surface_group", host)
     key = (tuple(float(w) for w in wavelengths),
            record if isinstance(record, bool) else tuple(record), bool(image_record))
+    if polarized:  # the coated / polarized trace's table (lowering checks its surfaces)
+        key = (*key, "polarized")
     cache = getattr(host, "_lowered", None)
     if not isinstance(cache, dict):
         cache = {}
@@ -363,7 +365,15 @@ def lens_for(optic_or_group, wavelengths, record=False, image_record=False):
             host._lowered = cache
         except AttributeError:
             pass
-    table = lower_surface_group(sg, wavelengths, record=record)
+    if not polarized:
+        # the callers of the plain kernels (analyses, sharded traces, the ops' plans) must
+        # not trace a coated or polarized lens as if it were neither
+        if getattr(host, "polarization", "ignore") != "ignore" or any(
+                getattr(s, "coating", None) is not None for s in sg.surfaces):
+            raise ValueError(
+                "this trace path does not support coatings or a polarization state; "
+                "Optic.trace, Optic.trace_generic and SurfaceGroup.trace do")
+    table = lower_surface_group(sg, wavelengths, record=record, polarized=polarized)
     table.apod = lower_apodization(host)
     if image_record:
         table.final_mat = -1
@@ -960,6 +970,11 @@ class RealRayTracer:
         Hx = np.atleast_1d(np.asarray(Hx, dtype=np.float64))
         Hy = np.atleast_1d(np.asarray(Hy, dtype=np.float64))
         Hx, Hy = np.broadcast_arrays(Hx, Hy)
+        from . import polarization
+
+        if polarization.needs_polarized_trace(optic):
+            # coatings / a polarization state: the F_POL kernel family (or its host build)
+            return self._trace_polarized(Hx, Hy, wavelength, num_rays, distribution, None)
         record = optic.surface_group.record
         dlens = lens_for(optic, [wavelength], record=True if record == "all" else False)
         segs = _cached_segments(optic, dlens, wavelength, Hx, Hy)
@@ -980,8 +995,36 @@ class RealRayTracer:
         self._record(dlens, out, rec, n, segs, px, py, n_p)
         return out
 
-    def trace_generic(self, Hx, Hy, Px, Py, wavelength, newton_mode="reference"):
-        """real_ray_tracer.py:99-133: per-ray field and pupil coordinates."""
+    def _trace_polarized(self, Hx, Hy, wavelength, num_rays, distribution, device):
+        """trace() of a coated / polarized Optic (polarization.trace_optic)."""
+        from . import polarization
+
+        optic = self.optic
+        polarization.check_polarization(optic)
+        EPL, EPD = pupil_scalars(optic)
+        segs = np.stack([segment_params(optic, float(hx), float(hy), 0, EPL, EPD)
+                         for hx, hy in zip(Hx, Hy, strict=True)])
+        if device is not None and torch.device(device).type == "cpu":
+            from .distribution import create_distribution
+
+            d = distribution
+            if isinstance(d, str):
+                d = create_distribution(d)
+                d.generate_points(num_rays)
+            px = torch.as_tensor(np.array(d.x, dtype=np.float64))
+            py = torch.as_tensor(np.array(d.y, dtype=np.float64))
+        else:
+            px, py = pupil_arrays(distribution, num_rays, get_device())
+        n_p = px.numel()
+        keys = [("trace-pol", tuple(np.round(Hx, 15)), tuple(np.round(Hy, 15)),
+                 float(wavelength), n_p)]
+        return polarization.trace_optic(optic, segs, px, py, n_p * len(segs), n_p, wavelength,
+                                        False, True, keys, device=device)
+
+    def trace_generic(self, Hx, Hy, Px, Py, wavelength, newton_mode="reference", _device=None):
+        """real_ray_tracer.py:99-133: per-ray field and pupil coordinates. (_device:
+        polarization.trace_generic's host-build switch for coated / polarized lenses.)"""
+        device = _device
         optic = self.optic
         _validate_normalized(Hx, Hy, "field")
         _validate_normalized(Px, Py, "pupil")
@@ -994,6 +1037,21 @@ class RealRayTracer:
         vys = np.array([v[1] for v in vig])
         Px = Px * (1 - vxs)
         Py = Py * (1 - vys)
+        from . import polarization
+
+        if polarization.needs_polarized_trace(optic):
+            polarization.check_polarization(optic)
+            EPL, EPD = pupil_scalars(optic)
+            segs = np.stack([segment_params(optic, float(hx), float(hy), 0, EPL, EPD)
+                             for hx, hy in zip(Hx, Hy, strict=True)])
+            cpu = device is not None and torch.device(device).type == "cpu"
+            dev = torch.device("cpu") if cpu else get_device()
+            px = torch.as_tensor(np.ascontiguousarray(Px), device=dev)
+            py = torch.as_tensor(np.ascontiguousarray(Py), device=dev)
+            # no intensity update here: the reference's trace_generic never calls it
+            return polarization.trace_optic(optic, segs, px, py, n, 1, wavelength, True, False,
+                                            [("generic-pol", float(wavelength), n)],
+                                            device=device)
         record = optic.surface_group.record
         dlens = lens_for(optic, [wavelength], record=True if record == "all" else False)
         EPL, EPD = pupil_scalars(optic)
@@ -1074,6 +1132,11 @@ class RealRayTracer:
 def trace_surface_group(sg, rays: RealRays, skip=0, newton_mode="reference"):
     """SurfaceGroup.trace(rays, skip) (surface_group.py:232-244): in-place trace of
     resident RealRays through the traced surfaces (no image-space propagate)."""
+    from . import polarization
+
+    if isinstance(rays, polarization.PolarizedRays) or any(
+            s.coating is not None for s in sg.surfaces[1:]):
+        return _trace_surface_group_polarized(sg, rays, skip)
     w = torch.unique(rays.w)
     # one wavelength: n / k from the per-wavelength tables (the common Optic.trace case);
     # several: every ray's own n(w), k(w) from the material tables in the kernel
@@ -1096,6 +1159,50 @@ def trace_surface_group(sg, rays: RealRays, skip=0, newton_mode="reference"):
                start_surface=max(int(skip) - 1, 0), per_ray_w=per_ray)
     if rec is not None:
         _record_into(sg, rec, n, table.rec_surfaces, rays0)
+    return rays
+
+
+def _trace_surface_group_polarized(sg, rays, skip):
+    """SurfaceGroup.trace of PolarizedRays, or of plain rays through coated surfaces
+    (ort_trace_sequential_polarized): the matrices of this call, started from the identity,
+    are multiplied onto rays.p. One wavelength per call."""
+    from . import polarization
+
+    polarized = isinstance(rays, polarization.PolarizedRays)
+    if not polarized and sg.uses_polarization:
+        raise ValueError("Polarization must be set when surfaces have "
+                         "polarization-dependent coatings.")
+    w = torch.unique(rays.w)
+    if w.numel() != 1:
+        raise ValueError("coated / polarized surfaces trace one wavelength per call")
+    dev = rays.x.device
+    table = lower_surface_group(sg, [float(w[0].item())], record=(sg.record == "all"),
+                                polarized=True)
+    table.final_mat = -1
+    if dev.type == "cpu":
+        from .host import HostLens
+
+        lens = HostLens(table)
+    else:
+        lens = DeviceLens(table, device=dev)
+    n = len(rays)
+    rec = None
+    if sg.record == "all":
+        rec = torch.empty(table.n_rec * 8 * n, dtype=torch.float64, device=dev)
+    rays_in = [getattr(rays, a).contiguous() for a in _abi.RAY_FIELDS]
+    mode = _abi.POL_MATRICES if polarized else _abi.POL_IGNORE
+    outs, planes = polarization.trace_sequential_polarized(
+        lens, rays_in, mode, None, rec=rec, want_p=polarized,
+        start_surface=max(int(skip) - 1, 0))
+    if rec is not None:
+        rays0 = RealRays.__new__(RealRays)
+        for a, t in zip(_abi.RAY_FIELDS, rays_in, strict=True):
+            setattr(rays0, a, t)
+        _record_into(sg, rec, n, table.rec_surfaces, rays0)
+    for a, t in zip(_abi.RAY_FIELDS, outs, strict=True):
+        setattr(rays, a, t)
+    if polarized:
+        rays.p = torch.matmul(polarization.planes_to_p(planes, n), rays.p)
     return rays
 
 

@@ -75,7 +75,7 @@ class Surface:
             interaction_model = RefractiveReflectiveModel(is_reflective=is_reflective)
         self.interaction_model = interaction_model
         interaction_model.parent_surface = self
-        self.previous_surface = previous_surface
+        self._previous_surface = previous_surface
         self._material_post = material_post
         self.is_stop = is_stop
         self.aperture = configure_aperture(aperture)
@@ -99,6 +99,45 @@ class Surface:
     @material_post.setter
     def material_post(self, m):
         self._material_post = m
+        self._refresh_fresnel()
+        # standard_surface.py:100-108, 158-159: the next surface's listener replaces ANY
+        # coating it has by the Fresnel coating of its (new) materials
+        nxt = getattr(self, "_next_surface", None)
+        if nxt is not None and nxt.coating is not None:
+            nxt.set_fresnel_coating()
+
+    @property
+    def previous_surface(self):
+        return self._previous_surface
+
+    @previous_surface.setter
+    def previous_surface(self, s):
+        """standard_surface.py:95-108, 133-141: linking a surface triggers its update
+        callback, which replaces ANY coating it has with the Fresnel coating of the
+        materials around it (so a coating handed to add_surface does not survive the
+        linking; one assigned to interaction_model.coating afterwards does)."""
+        self._previous_surface = s
+        if self.coating is not None:
+            self.set_fresnel_coating()
+
+    @property
+    def coating(self):
+        """standard_surface.py:161-164."""
+        return getattr(getattr(self, "interaction_model", None), "coating", None)
+
+    def set_fresnel_coating(self):
+        """standard_surface.py:260-264."""
+        from .polarization import FresnelCoating
+
+        self.interaction_model.coating = FresnelCoating(self.material_pre, self.material_post)
+
+    def _refresh_fresnel(self):
+        """standard_surface.py:153-157: a new material after the surface re-derives its
+        Fresnel coating."""
+        from .polarization import FresnelCoating
+
+        if isinstance(self.coating, FresnelCoating):
+            self.set_fresnel_coating()
 
     @property
     def is_reflective(self):
@@ -329,6 +368,21 @@ class SurfaceGroup:
     def _relink(self):
         for i, s in enumerate(self.surfaces):
             s.previous_surface = self.surfaces[i - 1] if i > 0 else None
+            s._next_surface = self.surfaces[i + 1] if i + 1 < len(self.surfaces) else None
+
+    @property
+    def uses_polarization(self):
+        """surface_group.py:187-193: some surface has a polarization-dependent coating."""
+        from .polarization import BaseCoatingPolarized
+
+        return any(isinstance(s.coating, BaseCoatingPolarized) for s in self.surfaces)
+
+    def set_fresnel_coatings(self):
+        """surface_group.py:369-373: Fresnel coatings on every surface whose materials
+        differ."""
+        for s in self.surfaces[1:-1]:
+            if s.material_pre.key() != s.material_post.key():  # materials/base.py:70-71
+                s.set_fresnel_coating()
 
     def _update_coordinate_systems(self, start_index):
         for i in range(max(start_index, 1), len(self.surfaces)):
@@ -381,11 +435,17 @@ class SurfaceGroup:
             interaction_type = "diffractive"
         elif kw.get("phase_profile") is not None:
             interaction_type = "phase"
-        for key in ("coating", "bsdf"):
-            if kw.get(key) is not None:
-                raise ValueError(f"{key} is out of scope for the trace core")
+        if kw.get("bsdf") is not None:
+            raise ValueError("bsdf is out of scope for the trace core")
+        # coating_factory.py:35-60: a coating object, or "fresnel" (the materials around the
+        # surface, known once it is linked: set after construction)
+        from .polarization import create_coating
+
+        # ("fresnel": the material before the surface is known once it is linked, and the
+        # linking re-derives the coating: Surface.previous_surface)
+        coating = create_coating(kw.get("coating"), material_post, material_post)
         model = make_interaction(interaction_type, is_reflective, focal_length=kw.get("f"),
-                                 phase_profile=kw.get("phase_profile"))
+                                 phase_profile=kw.get("phase_profile"), coating=coating)
         return Surface(None, material_post, geometry, is_stop=is_stop,
                        aperture=kw.get("aperture"), surface_type=surface_type,
                        comment=comment, interaction_model=model)
