@@ -12,8 +12,8 @@
  * CPU), and its backward under autograd (optimization/optimizer/torch/base.py:116-131).
  *
  * Same structs as optiland_rt.h, every pointer a HOST pointer. The per-ray arithmetic is
- * the GPU kernels' own source (csrc/ort_core.h, ort_interact.h, ort_material.h, and the
- * derivative sweeps of csrc/ort_sweep.h) compiled with g++ -ffp-contract=off, so a trace
+ * the GPU kernels' own source (csrc/ort_core.h, ort_interact.h, ort_material.h, the argument
+ * layer of csrc/ort_args.h and the derivative sweeps of csrc/ort_sweep.h) compiled with g++ -ffp-contract=off, so a trace
  * gives the GPU's bits. Newton surfaces follow the reference's global stop rule
  * (newton_raphson.py:137-166: stop when max |f| < tol over the rays of one trace call)
  * directly: every Newton group (batch->group_len rays) is stepped in lockstep, as the

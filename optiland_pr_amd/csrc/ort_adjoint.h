@@ -1,4 +1,6 @@
-// ort_adjoint.h -- the reverse-mode (adjoint) VJP kernels of the fused trace.
+// ort_adjoint.h -- the VJP kernels of the fused trace: the reverse-mode (adjoint) kernels
+// and, at the end, the forward-mode vjp_kernel / vjp_reduce_kernel. The only device header
+// that includes the sweeps (ort_sweep.h), so the trace units never parse them.
 //
 // The per-ray sweep (forward replay with a tape, then the adjoint of every step of
 // Surface.trace from the image back to the first surface) is adj_ray in ort_sweep.h,
@@ -9,7 +11,8 @@
 // slot sums weighted by the tangent tables, in fixed orders (deterministic).
 #pragma once
 
-#include "ort_kernels.h"  // (and ort_sweep.h: adj_ray, AArgs)
+#include "ort_kernels.h"
+#include "ort_sweep.h"  // adj_ray, vjp_ray (AArgs, JArgs: ort_args.h)
 
 namespace ortk {
 
@@ -181,6 +184,52 @@ __global__ __launch_bounds__(kBlock) ORT_ADJ_OCC void adj_kernel(const KArgs a, 
     double v = bpart_s[slot][0];
     for (int w = 1; w < kBlock / 64; ++w) v += bpart_s[slot][w];
     j.partial[(int64_t)slot * j.n_wave + blockIdx.x] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Forward-mode VJP (ORT_VJP_UNROLLED): vjp_ray (ort_sweep.h) per lane; each block writes
+// its P sums (wave sums, then the block's four waves in order) to partial[block][P] and
+// vjp_reduce_kernel adds, per parameter, the blocks' sums in index order to grad: the
+// same bits run to run (no atomics).
+// ---------------------------------------------------------------------------------
+template <int P, uint32_t KM>
+__global__ __launch_bounds__(kBlock) void vjp_kernel(const KArgs a, const JArgs j) {
+  const int64_t rid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool active = rid < a.n_rays;
+  double acc[P];
+  vjp_ray<P, KM>(a, j, rid, active, acc);
+  __shared__ double part[kBlock / 64][P];
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    const double v = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < P) {
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) v += part[w][threadIdx.x];
+    j.partial[(int64_t)blockIdx.x * P + threadIdx.x] = v;
+  }
+}
+
+// One block per parameter k < P of the chunk: grad[p0 + k] += the blocks' partials summed
+// in a fixed order (strided per thread, wave sums, the four waves in order).
+template <int P>
+__global__ __launch_bounds__(kBlock) void vjp_reduce_kernel(const JArgs j, int64_t n_block) {
+  const int k = blockIdx.x;
+  if (j.p0 + k >= j.n_param) return;  // uniform
+  double v = 0.0;
+  for (int64_t b = threadIdx.x; b < n_block; b += kBlock) v += j.partial[b * P + k];
+  v = wave_sum(v);
+  __shared__ double ws[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int w = 0; w < kBlock / 64; ++w) s += ws[w];
+    j.grad[j.p0 + k] += s;
   }
 }
 

@@ -1,6 +1,9 @@
 // ort_api.hip -- the C ABI (include/optiland_rt.h): argument checks, lens / batch
-// unpacking and kernel launches. Kernels are reached through the select_* functions of
-// ort_kernels.h (their templates are instantiated in the ort_k_*.hip units).
+// unpacking and kernel launches. The unpacking and every check the host library
+// (ort_host.cpp) makes too are ort_args.h's (fill_args, fill_pol, the VJP front end); this
+// file adds what depends on device memory and the launches. Kernels are reached through the
+// select_* functions of ort_kernels.h (their templates are instantiated in the ort_k_*.hip
+// units).
 
 #include "ort_adjoint.h"
 
@@ -230,10 +233,14 @@ static bool adj_layout(const ort_lens* lens, const ort_batch* batch,
     L.total = al(L.n_wave * 4 * (int64_t)sizeof(double));
     return true;
   }
+  // (vjp_fill_adjoint makes this check for a VJP call; this copy serves
+  // ort_vjp_workspace_size, which has no other)
   if (params->n_mono < 0 || (params->n_mono > 0 && !params->zern_param)) return false;
-  L.n_slot = (int32_t)(3 * S + params->n_zern + 1 + params->n_mono);
-  // partial columns: one per block (its waves combined in LDS, ort_adjoint.h)
-  if (L.n_slot > kBlockSlots) return false;  // the forward-mode VJP serves such lenses
+  L.n_slot = vjp_slot_count(lens->n_surfaces, params);
+  // device only: partial columns are one per block (its waves combined in LDS,
+  // ort_adjoint.h), so the slots must fit the block's LDS rows; the forward-mode VJP serves
+  // lenses past that (the host library has no such limit and takes them in adjoint mode)
+  if (L.n_slot > kBlockSlots) return false;
   L.n_wave = (n + kBlock - 1) / kBlock;
   L.tape = 0;
   // a tape the primal wrote (params->tape) lives outside the workspace
@@ -258,76 +265,59 @@ int64_t ort_vjp_workspace_size(const ort_lens* lens, const ort_batch* batch,
 }
 
 // Shared body of the two VJP entry points: generated rays (px, py) or resident rays
-// (rays_in, resident = true).
+// (rays_in, resident = true). The checks and assignments the host library makes too are
+// ort_args.h's front end (vjp_check_call, vjp_prepare, vjp_fill_*); what follows them here
+// is the device's own: the workspace, a tape the primal wrote, the launches, and the
+// refusals marked "device only".
 static int vjp_run(const ort_lens* lens, const double* px, const double* py,
                    const ort_rays* rays_in, bool resident, const ort_batch* batch,
                    const ort_options* opt, const ort_vjp_params* params,
                    const ort_rays* cotangent, const double* rec_cotangent, const double* rec,
                    double* grad, const ort_rays* grad_in, void* stream) {
-  if (!batch || !cotangent || !params || params->n_param < 0) return ORT_ERR_ARG;
+  bool want_in = false, nothing = false;
+  int rc = vjp_check_call(batch, params, cotangent, grad, grad_in, want_in, nothing);
+  if (rc) return rc;
   const int32_t n_param = params->n_param;
-  const bool want_in = grad_in && (grad_in->x || grad_in->y || grad_in->z || grad_in->L ||
-                                   grad_in->M || grad_in->N || grad_in->i || grad_in->opd);
-  if (n_param > 0 && !grad) return ORT_ERR_ARG;
-  if (batch->n_rays == 0 || (n_param == 0 && !want_in)) {
-    // nothing to trace: an overwritten gradient is zero
+  hipStream_t s = (hipStream_t)stream;
+  // device only: an empty call returns before the rays, options and lens are looked at (the
+  // host library checks them first), zeroing an overwritten gradient on the way out
+  if (nothing) {
     if (params->grad_init && n_param > 0 &&
-        hipMemsetAsync(grad, 0, (size_t)n_param * sizeof(double), (hipStream_t)stream) !=
-            hipSuccess)
+        hipMemsetAsync(grad, 0, (size_t)n_param * sizeof(double), s) != hipSuccess)
       return ORT_ERR_LAUNCH;
     return ORT_OK;
   }
-  if (rec_cotangent && !rec) return ORT_ERR_ARG;  // intensity rows weight the absorption
-  if (resident) {
-    if (!rays_in) return ORT_ERR_ARG;
-  } else if (!px || !py || !batch->seg || batch->w) {
-    return ORT_ERR_ARG;
-  }
+  if (!vjp_inputs_ok(resident, rays_in, px, py, batch)) return ORT_ERR_ARG;
   KArgs a{};
   uint32_t feat = 0;
-  if (opt && opt->verify_stats) return ORT_ERR_ARG;  // trace launches only
-  int rc = fill_args(a, lens, batch, opt, nullptr, nullptr, nullptr, feat);
-  if (rc) return rc;
+  if ((rc = vjp_prepare(a, feat, lens, px, py, rays_in, resident, batch, opt, params,
+                        rec_cotangent, rec)))
+    return rc;
+  // device only: the kernels differentiate the unrolled updates of the schedule the primal
+  // ran (opt->sched); a wave-stopped trace has no such counts (the host library steps its
+  // Newton groups by the reference's stop rule whatever the mode says)
   if (opt->newton_mode != ORT_NEWTON_SCHEDULE) return ORT_ERR_ARG;
-  if (params->zern_param && (feat & ort::KM_ZERN) == 0) return ORT_ERR_ARG;
-  // thin-lens / phase / grating surfaces: the forward-mode VJP only (vjp_ray's all-kinds
-  // instantiation carries their interactions in duals; the adjoint has no reverse for them)
-  if ((feat & F_IA) && params->mode != ORT_VJP_UNROLLED) return ORT_ERR_ARG;
-  if (lens->geometry_mask & ((1u << ORT_GEOM_GRID_SAG) | (1u << ORT_GEOM_NURBS)))
-    return ORT_ERR_ARG;  // nor grid sags / NURBS (no derivative kernels)
-  if (resident) {
-    a.in = *rays_in;
-  } else {
-    a.px = px;
-    a.py = py;
-  }
   const int64_t blocks = (a.n_rays + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffff) return ORT_ERR_ARG;
   const uint32_t km = (feat & F_IA) ? 15u : (feat & F_KM);  // (F_IA: every kind, vjp_ray)
-  hipStream_t s = (hipStream_t)stream;
+  AdjLayout L;
   if (params->mode == ORT_VJP_ADJOINT) {
-    AdjLayout L;
+    AArgs aj{};
+    if ((rc = vjp_fill_adjoint(aj, lens, params, cotangent, rec_cotangent, rec, grad, grad_in,
+                               want_in)))
+      return rc;
     if (!adj_layout(lens, batch, params, L)) return ORT_ERR_ARG;
     if (!params->workspace || params->workspace_size < L.total) return ORT_ERR_ARG;
     char* w = (char*)params->workspace;
-    AArgs aj{};
-    aj.zparam = params->zern_param;
-    aj.tan_surf = params->surf_tangent;
-    aj.tan_final = params->final_tangent;
-    aj.n_param = n_param;
-    aj.n_zern = params->n_zern;
-    aj.n_slot = L.n_slot;
-    aj.n_surf = lens->n_surfaces;
     aj.n_wave = L.n_wave;
-    aj.cot = *cotangent;
-    aj.rec_cot = rec_cotangent;
-    aj.rec = rec;
-    if (want_in) aj.gin = *grad_in;
     aj.tape = (double*)(w + L.tape);
-    if (params->tape) {  // the primal wrote the tape: reverse sweep only
+    // device only: the primal wrote the tape (F_TAPE): reverse sweep only. The host library
+    // refuses a tape and always replays the forward.
+    if (params->tape) {
       if (resident || !params->primal.L || !params->primal.M || !params->primal.N ||
           !params->primal.i)
         return ORT_ERR_ARG;
+      if (params->rms_stats && (!params->primal.x || !params->primal.y)) return ORT_ERR_ARG;
       aj.tape = (double*)params->tape;
       aj.tape_ready = 1;
       aj.primal = params->primal;
@@ -336,45 +326,25 @@ static int vjp_run(const ort_lens* lens, const double* px, const double* py,
     aj.slot_sum = (double*)(w + L.slot_sum);
     aj.need = params->slot_need;  // NULL: adj_run derives it into the workspace
     aj.zero_partials = opt->start_surface > 0;
-    aj.grad = grad;
     aj.grad_store = params->grad_init != 0;
-    aj.n_mono = params->n_mono;
-    aj.surf = lens->surfaces;
-    aj.zern = lens->zern;
-    aj.coef = lens->coef;
-    // an rms spot size's cotangent folded into the x, y cotangent load
-    if ((params->rms_stats != nullptr) != (params->rms_grad != nullptr)) return ORT_ERR_ARG;
-    if (params->rms_stats && aj.tape_ready && (!params->primal.x || !params->primal.y))
-      return ORT_ERR_ARG;
-    aj.rms_stats = params->rms_stats;
-    aj.rms_grad = params->rms_grad;
     // radius / conic tangents need duals seeded on them too
     return adj_run(a, aj, (int32_t*)(w + L.need), params->surf_tangent ? 4 : 2, km, resident,
                    blocks, s);
   }
   if (params->mode != ORT_VJP_UNROLLED) return ORT_ERR_ARG;
-  if (want_in) return ORT_ERR_ARG;  // forward mode carries parameter tangents only
-  if (params->rms_stats || params->rms_grad) return ORT_ERR_ARG;  // the adjoint's fold only
-  AdjLayout L;
+  JArgs j{};
+  if ((rc = vjp_fill_unrolled(j, params, cotangent, rec_cotangent, grad, want_in))) return rc;
   if (!adj_layout(lens, batch, params, L)) return ORT_ERR_ARG;
   if (!params->workspace || params->workspace_size < L.total) return ORT_ERR_ARG;
-  JArgs j{};
-  j.zparam = params->zern_param;
-  j.tan_surf = params->surf_tangent;
-  j.tan_final = params->final_tangent;
-  j.n_param = n_param;
-  j.cot = *cotangent;
-  j.rec_cot = rec_cotangent;
-  j.grad = grad;
   j.partial = (double*)params->workspace;
   if (params->grad_init &&
       hipMemsetAsync(grad, 0, (size_t)n_param * sizeof(double), s) != hipSuccess)
     return ORT_ERR_LAUNCH;
+  // tangents per launch: ORT_VJP_TANGENTS overrides (A/B timing)
+  const char* e = getenv("ORT_VJP_TANGENTS");
+  const int pref = e ? atoi(e) : 4;
   for (int p0 = 0; p0 < n_param;) {
     const int left = n_param - p0;
-    // tangents per launch: ORT_VJP_TANGENTS overrides (A/B timing)
-    const char* e = getenv("ORT_VJP_TANGENTS");
-    const int pref = e ? atoi(e) : 4;
     const int P = left >= 4 && pref >= 4 ? 4 : (left >= 2 && pref >= 2 ? 2 : 1);
     VjpFn fn = select_vjp(P, km);
     VjpReduceFn red = select_vjp_reduce(P);
@@ -461,7 +431,6 @@ int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,
   a.seg = batch->seg;
   a.pupil_per_ray = batch->pupil_per_ray;
   a.apod = batch->apod;
-  if (a.n_rays == 0) return ORT_OK;
   const int64_t blocks = (a.n_rays + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(select_generate(), dim3((unsigned)blocks), dim3(kBlock), 0,
                      (hipStream_t)stream, a);

@@ -2042,7 +2042,7 @@ ORT_INLINE double grid_final(const GridView& g, const Ray& r, double t) {
 // only pays registers for the kinds it contains.
 // KM_FREE covers the freeform kinds (XY polynomial, Chebyshev, biconic, toroidal, Forbes
 // Q-bfs / Q-2D, grid sag) with a runtime switch; KM_NURBS the NURBS surfaces.
-// KM_NURBS (bit 16, clear of the kernels' other specialisation bits, ort_sweep.h): NURBS
+// KM_NURBS (bit 16, clear of the kernels' other specialisation bits, ort_args.h): NURBS
 // surfaces, compiled only into the kernels of lenses that have one (ort_k_trace_ia.hip,
 // ort_k_geom.hip)
 enum : unsigned { KM_EVEN = 1u, KM_ODD = 2u, KM_ZERN = 4u, KM_FREE = 8u, KM_NURBS = 1u << 16 };

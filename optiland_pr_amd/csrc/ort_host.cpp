@@ -2,9 +2,11 @@
 // the CPU dispatch key of torch.ops.ort.trace_sequential and of its VJP.
 //
 // Compiled with g++ -O2 -ffp-contract=off -fopenmp (optiland_pr_amd/build.py), from the
-// same per-ray sources as the HIP kernels (ort_core.h, ort_interact.h, ort_material.h and
-// the derivative sweeps of ort_sweep.h), so every value is the GPU's. What is host-specific
-// is the control around the per-ray code:
+// same sources as the HIP kernels: the per-ray arithmetic (ort_core.h, ort_interact.h,
+// ort_material.h, ort_polar.h), the argument unpacking, the surface step after the distance
+// (interact, pol_step) and the VJP front end (ort_args.h), and the derivative sweeps
+// (ort_sweep.h) -- so every value is the GPU's and an argument is checked by the code that
+// checks it there. What is host-specific is the control around the per-ray code:
 //   * Newton surfaces: the reference's global stop rule (newton_raphson.py:137-166, the
 //     test max |f| < tol over every ray of the call, NaN never passing; grid_sag.py:108-140
 //     the test max |dt| < tol after each update) evaluated directly, the rays of one Newton
@@ -14,9 +16,9 @@
 //     (trace_kernel<F_IA>: propagate, normalise after a thin lens, OPD, clip, interact,
 //     globalize, record), which for refractive / reflective surfaces is finish_surface;
 //   * the VJPs run adj_ray / vjp_ray per ray with a host lane (ray-local tape, per-chunk
-//     slot accumulators) and reduce the chunks in index order;
-//   * one specialisation with every Newton kind compiled in (the GPU's per-lens KM
-//     specialisations only prune code: the values are the same).
+//     slot accumulators) and reduce the chunks in index order; the refusals only this
+//     library makes are named in host_vjp_run;
+//   * one specialisation with every Newton kind compiled in (kAllKinds).
 #define ORT_HD
 #include "../../include/optiland_host.h"
 
@@ -35,8 +37,6 @@ namespace {
 using namespace ortk;
 using ort::Ray;
 
-constexpr unsigned kAllKinds =
-    ort::KM_EVEN | ort::KM_ODD | ort::KM_ZERN | ort::KM_FREE | ort::KM_NURBS;
 constexpr int64_t kChunk = 256;  // rays per reduction chunk (the GPU's block)
 constexpr int64_t kParMin = 2048;  // below this many rays a phase runs on one thread
 
@@ -45,42 +45,6 @@ int g_threads = 0;
 int threads_for(int64_t n) {
   if (n < kParMin) return 1;
   return g_threads > 0 ? g_threads : omp_get_max_threads();
-}
-
-bool is_newton(int g) {
-  return g != ORT_GEOM_PLANE && g != ORT_GEOM_STANDARD && g != ORT_GEOM_NURBS;
-}
-
-int range_bit(const ort_surface& s) {
-  return s.geometry == ORT_GEOM_CHEBYSHEV ? (int)ORT_STATUS_CHEBYSHEV_RANGE
-                                          : (int)ORT_STATUS_ZERNIKE_RANGE;
-}
-
-// the interaction after propagation, OPD and clipping (trace_kernel<F_IA>'s interact,
-// ort_kernels.h): standard_surface.py:225 -> interactions/*.py
-void interact(const KArgs& a, const ort_surface& s, Ray& r, const ort_surface_optics& o,
-              int lam, double wl, bool& unnorm) {
-  const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
-  const double* p = a.coef + s.ia_off;
-  if (s.interaction == ORT_IA_THIN_LENS) {
-    ort::thin_lens(r, p[0], o.n_pre, refl ? -o.n_pre : o.n_post);
-    unnorm = true;
-    return;
-  }
-  double nx, ny, nz;
-  ort::surface_normal<kAllKinds>(s, s.radius, s.conic, a.coef, a.zern, kNoSeed, r, nx, ny, nz);
-  if (s.interaction == ORT_IA_REFRACT_REFLECT) {
-    if (refl)
-      ort::reflect(r, nx, ny, nz);
-    else
-      ort::refract(r, nx, ny, nz, o.u);
-    return;
-  }
-  const double w = a.w ? wl : (a.n_lambda == 1 ? a.lambdas[0] : a.lambdas[lam]);
-  if (s.interaction == ORT_IA_PHASE)
-    ort::phase_interact(r, p, nx, ny, nz, o.n_pre, refl ? o.n_pre : o.n_post, refl, w);
-  else
-    ort::diffract(r, p, nx, ny, nz, o.n_pre, o.n_post, refl, w);
 }
 
 ort_surface_optics optics_of(const KArgs& a, const ort_surface& s, int si, int lam, double wl) {
@@ -102,21 +66,13 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
     if (a.seg) lam[k] = a.seg[a.n_seg == 1 ? 0 : r / a.seg_len].lambda_idx;
     if (a.w) wl[k] = a.w[r];
     Ray& q = rays[k];
-    q.x = a.in.x[r];
-    q.y = a.in.y[r];
-    q.z = a.in.z[r];
-    q.L = a.in.L[r];
-    q.M = a.in.M[r];
-    q.N = a.in.N[r];
-    q.i = a.in.i[r];
-    q.opd = a.in.opd[r];
-    q.att = 0.0;
+    load_ray(a, r, q);
     if (a.coat) ort::pol_init(pol[k], q.L, q.M, q.N, q.i);
   }
   for (int si = a.start_surface; si < a.n_surf; ++si) {
     const ort_surface s = a.surf[si];
     if (updates) updates[si] = 0;
-    const bool known = s.geometry >= ORT_GEOM_PLANE && s.geometry <= ORT_GEOM_NURBS;
+    const bool known = known_geometry(s.geometry);
     if (!known) status |= ORT_STATUS_BAD_GEOMETRY;
     const bool grid = s.geometry == ORT_GEOM_GRID_SAG;
     // localize and the closed-form distance (the Newton kinds' initial guess)
@@ -159,7 +115,7 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
 #pragma omp parallel for num_threads(nt) schedule(static)
       for (int64_t k = 0; k < n; ++k) t[k] = ort::grid_final(g, rays[k], t[k]);
       if (updates) updates[si] = j;
-    } else if (known && is_newton(s.geometry)) {
+    } else if (known && scheduled_geometry(s.geometry)) {
       // newton_raphson.py:137-166: stop when max |f| < tol over the whole call
       f.resize(n);
       nx.resize(n);
@@ -206,42 +162,16 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, a.coef + s.ap_off, s.ap_len);
       bool un = false;
-      if (a.coat) {
-        // trace_kernel<F_POL>'s step (refractive / reflective surfaces only): interact()'s
-        // operations on the ray, the normal and the incoming direction kept
+      if (a.coat) {  // trace_kernel<F_POL>'s step (refractive / reflective surfaces only)
         double ux, uy, uz;
-        ort::surface_normal<kAllKinds>(s, s.radius, s.conic, a.coef, a.zern, kNoSeed, r, ux, uy,
-                                       uz);
-        const double k0x = r.L, k0y = r.M, k0z = r.N;
-        const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
-        if (refl)
-          ort::reflect(r, ux, uy, uz);
-        else
-          ort::refract(r, ux, uy, uz, o.u);
-        const ort_coating ct = a.coat[si];
-        double n1 = 1.0, n2 = 1.0;
-        if (ct.kind == ORT_COAT_FRESNEL) {
-          n1 = tab(a.n_tab, a.n_lambda, a.n_mat, lam[k], ct.mat_pre);
-          n2 = tab(a.n_tab, a.n_lambda, a.n_mat, lam[k], ct.mat_post);
-        }
-        ort::pol_surface(pol[k], ct, refl, ux, uy, uz, k0x, k0y, k0z, r.L, r.M, r.N, n1, n2,
-                         r.i);
-      } else {
-        interact(a, s, r, o, lam[k], wl[k], un);
-      }
+        pol_step<kAllKinds>(a, s, o, si, lam[k], r, pol[k], false, ux, uy, uz);
+      } else if (a.w)
+        interact<kAllKinds, true>(a, s, r, o, lam[k], wl[k], un);
+      else
+        interact<kAllKinds, false>(a, s, r, o, lam[k], wl[k], un);
       if (un) unnorm[k] = 1;
       globalize(a, s, r);
-      if (a.rec && (s.flags & ORT_SURF_RECORD)) {
-        double* b = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + r0 + k;
-        b[0 * a.n_rays] = r.x;
-        b[1 * a.n_rays] = r.y;
-        b[2 * a.n_rays] = r.z;
-        b[3 * a.n_rays] = r.L;
-        b[4 * a.n_rays] = r.M;
-        b[5 * a.n_rays] = r.N;
-        b[6 * a.n_rays] = ort::intensity(r);
-        b[7 * a.n_rays] = r.opd;
-      }
+      if (a.rec && (s.flags & ORT_SURF_RECORD)) store_record<PlainStore>(a, s, r0 + k, r);
     }
   }
   // real_ray_tracer.py:84-89: image-space propagate (final_mat < 0: none)
@@ -256,16 +186,12 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
       if (unnorm[k]) ort::normalize_dir(r);
     }
     const int64_t q = r0 + k;
-    a.out.x[q] = r.x;
-    a.out.y[q] = r.y;
-    a.out.z[q] = r.z;
-    a.out.L[q] = r.L;
-    a.out.M[q] = r.M;
-    a.out.N[q] = r.N;
-    a.out.i[q] = ort::intensity(r);
-    a.out.opd[q] = r.opd;
-    if (a.coat) {
-      a.out.i[q] = ort::pol_intensity(pol[k], a.pol_mode, a.pol_ex, a.pol_ey, ort::intensity(r));
+    if (!a.coat) {
+      store_ray<PlainStore>(a, q, r);
+    } else {
+      const double inten =
+          ort::pol_intensity(pol[k], a.pol_mode, a.pol_ex, a.pol_ey, ort::intensity(r));
+      store_ray<PlainStore>(a, q, r, &inten);
       if (a.p_out) {
         for (int e = 0; e < 9; ++e) {
           a.p_out[(int64_t)(2 * e) * a.n_rays + q] = pol[k].re[e];
@@ -403,36 +329,52 @@ int ort_host_trace_sequential_polarized(const ort_lens* lens, const ort_rays* ra
 
 namespace {
 
-// The shared body of the two host VJPs: resident rays (rays_in, RES) or rays generated from
-// pupil samples (a.px / a.py, the batch's segments: ort_trace_pupil_vjp's counterpart)
-template <bool RES>
-int host_vjp(KArgs& a, const ort_lens* lens, const ort_vjp_params* params,
-             const ort_rays* cotangent, const double* rec_cotangent, const double* rec,
-             double* grad, const ort_rays* grad_in, bool want_in) {
+// Shared body of the two host VJP entry points: resident rays (rays_in, resident = true) or
+// rays generated from pupil samples (px, py, the batch's segments: ort_trace_pupil_vjp's
+// counterpart). The checks and assignments the device library makes too are ort_args.h's
+// front end (vjp_check_call, vjp_prepare, vjp_fill_*); what follows them here is the
+// host's own: the need[] flags, the chunk loops and reductions, and the refusals marked
+// "host only".
+int host_vjp_run(const ort_lens* lens, const double* px, const double* py,
+                 const ort_rays* rays_in, bool resident, const ort_batch* batch,
+                 const ort_options* opt, const ort_vjp_params* params,
+                 const ort_rays* cotangent, const double* rec_cotangent, const double* rec,
+                 double* grad, const ort_rays* grad_in) {
+  bool want_in = false, nothing = false;
+  int rc = vjp_check_call(batch, params, cotangent, grad, grad_in, want_in, nothing);
+  if (rc) return rc;
+  // host only: the options and the rays are required of an empty call too (the device
+  // library returns ORT_OK for one before it looks at them)
+  if (!opt || !vjp_inputs_ok(resident, rays_in, px, py, batch)) return ORT_ERR_ARG;
   const int32_t n_param = params->n_param;
+  // host only: an overwritten gradient is zeroed here, before anything is traced, and the
+  // sums below accumulate (the device zeroes it in the empty return and otherwise hands
+  // grad_init to its reduce kernels: the same outcome)
+  if (params->grad_init)
+    for (int p = 0; p < n_param; ++p) grad[p] = 0.0;
+  if (nothing) return ORT_OK;
+  // host only: no tape -- the trace writes none (opt->tape) and the adjoint always replays
+  // the forward (params->tape); the device library takes both
+  if (opt->tape || params->tape) return ORT_ERR_ARG;
+  // host only: a generated-ray VJP starts at the first surface (the device library replays
+  // from opt->start_surface)
+  if (!resident && opt->start_surface) return ORT_ERR_ARG;
+  KArgs a{};
+  uint32_t feat = 0;
+  if ((rc = vjp_prepare(a, feat, lens, px, py, rays_in, resident, batch, opt, params,
+                        rec_cotangent, rec)))
+    return rc;
+  // (host only by omission: opt->newton_mode is not looked at -- the sweeps replay
+  // opt->sched or the surfaces' max_iter -- and a lens past the device's LDS slot limit,
+  // ORT_VJP_ADJOINT_MAX_SLOTS, is served in adjoint mode.)
   const int64_t n_chunk = (a.n_rays + kChunk - 1) / kChunk;
   if (params->mode == ORT_VJP_ADJOINT) {
     AArgs j{};
-    j.zparam = params->zern_param;
-    j.tan_surf = params->surf_tangent;
-    j.tan_final = params->final_tangent;
-    j.n_param = n_param;
-    j.n_zern = params->n_zern;
-    if (params->n_mono < 0 || (params->n_mono > 0 && !params->zern_param)) return ORT_ERR_ARG;
-    j.n_slot = 3 * a.n_surf + params->n_zern + 1 + params->n_mono;
-    j.n_surf = a.n_surf;
-    j.n_mono = params->n_mono;
-    j.surf = lens->surfaces;
-    j.zern = lens->zern;
-    j.coef = lens->coef;
+    if ((rc = vjp_fill_adjoint(j, lens, params, cotangent, rec_cotangent, rec, grad, grad_in,
+                               want_in)))
+      return rc;
     j.mono_on = mono_enabled(j);
-    if ((params->rms_stats != nullptr) != (params->rms_grad != nullptr)) return ORT_ERR_ARG;
-    j.rms_stats = params->rms_stats;  // replayed: the final point is the traced state
-    j.rms_grad = params->rms_grad;
-    j.cot = *cotangent;
-    j.rec_cot = rec_cotangent;
-    j.rec = rec;
-    if (want_in) j.gin = *grad_in;
+    // (rms_stats / rms_grad: the forward is replayed, so the final point is the traced state)
     std::vector<int32_t> need(j.n_slot, 0);
     for (int slot = 0; slot < j.n_slot; ++slot) {
       if (params->slot_need) {
@@ -444,9 +386,11 @@ int host_vjp(KArgs& a, const ort_lens* lens, const ort_vjp_params* params,
     j.need = need.data();
     std::vector<double> part((size_t)n_chunk * j.n_slot, 0.0);
     if (params->surf_tangent)
-      adj_chunks<kAllKinds, 4, RES>(a, j, part, n_chunk);
+      resident ? adj_chunks<kAllKinds, 4, true>(a, j, part, n_chunk)
+               : adj_chunks<kAllKinds, 4, false>(a, j, part, n_chunk);
     else
-      adj_chunks<kAllKinds, 2, RES>(a, j, part, n_chunk);
+      resident ? adj_chunks<kAllKinds, 2, true>(a, j, part, n_chunk)
+               : adj_chunks<kAllKinds, 2, false>(a, j, part, n_chunk);
     // grad[p] += sum over slots of d slot / d p * (the chunks' sums in index order)
     std::vector<double> slot_sum(j.n_slot, 0.0);
     for (int slot = 0; slot < j.n_slot; ++slot) {
@@ -466,16 +410,8 @@ int host_vjp(KArgs& a, const ort_lens* lens, const ort_vjp_params* params,
     return ORT_OK;
   }
   if (params->mode != ORT_VJP_UNROLLED) return ORT_ERR_ARG;
-  if (want_in) return ORT_ERR_ARG;  // forward mode carries parameter tangents only
-  if (params->rms_stats || params->rms_grad) return ORT_ERR_ARG;  // the adjoint's fold only
   JArgs j{};
-  j.zparam = params->zern_param;
-  j.tan_surf = params->surf_tangent;
-  j.tan_final = params->final_tangent;
-  j.n_param = n_param;
-  j.cot = *cotangent;
-  j.rec_cot = rec_cotangent;
-  j.grad = grad;
+  if ((rc = vjp_fill_unrolled(j, params, cotangent, rec_cotangent, grad, want_in))) return rc;
   std::vector<double> part((size_t)n_chunk * 4);
   for (int p0 = 0; p0 < n_param; p0 += 4) {
     j.p0 = p0;
@@ -526,28 +462,8 @@ int ort_host_trace_sequential_vjp(const ort_lens* lens, const ort_rays* rays_in,
                                   const ort_vjp_params* params, const ort_rays* cotangent,
                                   const double* rec_cotangent, const double* rec,
                                   double* grad, const ort_rays* grad_in) {
-  if (!batch || !cotangent || !params || params->n_param < 0 || !rays_in || !opt)
-    return ORT_ERR_ARG;
-  const int32_t n_param = params->n_param;
-  const bool want_in = grad_in && (grad_in->x || grad_in->y || grad_in->z || grad_in->L ||
-                                   grad_in->M || grad_in->N || grad_in->i || grad_in->opd);
-  if (n_param > 0 && !grad) return ORT_ERR_ARG;
-  if (params->grad_init && n_param > 0)
-    for (int p = 0; p < n_param; ++p) grad[p] = 0.0;
-  if (batch->n_rays == 0 || (n_param == 0 && !want_in)) return ORT_OK;
-  if (rec_cotangent && !rec) return ORT_ERR_ARG;
-  if (opt->verify_stats || opt->tape || params->tape) return ORT_ERR_ARG;
-  KArgs a{};
-  uint32_t feat = 0;
-  int rc = fill_args(a, lens, batch, opt, nullptr, nullptr, nullptr, feat);
-  if (rc) return rc;
-  if (params->zern_param && (feat & ort::KM_ZERN) == 0) return ORT_ERR_ARG;
-  // thin-lens / phase / grating surfaces: the forward-mode VJP only (vjp_ray in duals)
-  if ((feat & F_IA) && params->mode != ORT_VJP_UNROLLED) return ORT_ERR_ARG;
-  if (lens->geometry_mask & ((1u << ORT_GEOM_GRID_SAG) | (1u << ORT_GEOM_NURBS)))
-    return ORT_ERR_ARG;  // nor grid sags / NURBS (no derivative kernels)
-  a.in = *rays_in;
-  return host_vjp<true>(a, lens, params, cotangent, rec_cotangent, rec, grad, grad_in, want_in);
+  return host_vjp_run(lens, nullptr, nullptr, rays_in, true, batch, opt, params, cotangent,
+                      rec_cotangent, rec, grad, grad_in);
 }
 
 // shared body of ort_host_trace_pupil and its polarized form
@@ -618,25 +534,8 @@ int ort_host_trace_pupil_vjp(const ort_lens* lens, const double* px, const doubl
                              const ort_batch* batch, const ort_options* opt,
                              const ort_vjp_params* params, const ort_rays* cotangent,
                              double* grad) {
-  if (!px || !py || !batch || !batch->seg || batch->w || !cotangent || !params ||
-      params->n_param < 0 || !opt)
-    return ORT_ERR_ARG;
-  const int32_t n_param = params->n_param;
-  if (n_param > 0 && !grad) return ORT_ERR_ARG;
-  if (params->grad_init && n_param > 0)
-    for (int p = 0; p < n_param; ++p) grad[p] = 0.0;
-  if (batch->n_rays == 0 || n_param == 0) return ORT_OK;
-  if (opt->verify_stats || opt->tape || params->tape || opt->start_surface) return ORT_ERR_ARG;
-  KArgs a{};
-  uint32_t feat = 0;
-  int rc = fill_args(a, lens, batch, opt, nullptr, nullptr, nullptr, feat);
-  if (rc) return rc;
-  if (params->zern_param && (feat & ort::KM_ZERN) == 0) return ORT_ERR_ARG;
-  if ((feat & F_IA) && params->mode != ORT_VJP_UNROLLED) return ORT_ERR_ARG;
-  if (lens->geometry_mask & ((1u << ORT_GEOM_GRID_SAG) | (1u << ORT_GEOM_NURBS))) return ORT_ERR_ARG;
-  a.px = px;
-  a.py = py;
-  return host_vjp<false>(a, lens, params, cotangent, nullptr, nullptr, grad, nullptr, false);
+  return host_vjp_run(lens, px, py, nullptr, false, batch, opt, params, cotangent, nullptr,
+                      nullptr, grad, nullptr);
 }
 
 // RayOperand.rms_spot_size (optimization/operand/ray.py:300-340) on host memory: the mean

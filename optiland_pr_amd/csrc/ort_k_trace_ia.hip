@@ -9,7 +9,7 @@ namespace ortk {
 
 KernelFn select_trace_ia(uint32_t feat) {
   constexpr uint32_t kAll = 15u;  // every Newton kind
-  if (feat & ort::KM_NURBS) {  // lenses with NURBS surfaces (ort_sweep.h fill_args)
+  if (feat & ort::KM_NURBS) {  // lenses with NURBS surfaces (ort_args.h fill_args)
     switch (feat & (F_GEN | F_REC | F_WRAY)) {
 #define ORT_C(F) \
   case (F):      \

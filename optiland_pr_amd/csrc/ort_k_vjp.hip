@@ -1,7 +1,7 @@
 // ort_k_vjp.hip -- VJP kernel selection by tangent count
-// (kernel templates: ort_kernels.h; compiled as its own translation unit)
+// (kernel templates: ort_adjoint.h; compiled as its own translation unit)
 
-#include "ort_kernels.h"
+#include "ort_adjoint.h"
 
 namespace ortk {
 VjpFn select_vjp1(uint32_t km);

@@ -1,7 +1,7 @@
 // ort_k_vjp4.hip -- autograd VJP kernels (16 Newton-kind specialisations) with 4 tangent(s) per launch
-// (kernel templates: ort_kernels.h; compiled as its own translation unit)
+// (kernel templates: ort_adjoint.h; compiled as its own translation unit)
 
-#include "ort_kernels.h"
+#include "ort_adjoint.h"
 
 namespace ortk {
 VjpFn select_vjp4(uint32_t km) {

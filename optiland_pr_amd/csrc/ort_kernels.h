@@ -2,7 +2,10 @@
 //
 // Shared by the kernel translation units (ort_k_*.hip, compiled in parallel, each
 // instantiating one family of specialisations) and the C ABI (ort_api.hip), which only
-// reaches kernels through the select_* functions declared at the end.
+// reaches kernels through the select_* functions declared at the end. The argument blocks
+// and every per-ray piece the host library runs too (localize / globalize, interact,
+// pol_step, the geometry predicates, the ray load / store) come from ort_args.h; what is
+// here is the device side: wave operations, the Newton schedule protocol, the kernels.
 //
 // One ray per lane, all surfaces fused in one launch. The ray state
 // (x, y, z, L, M, N, i, opd) stays in VGPRs from the first surface to the image; the
@@ -25,11 +28,11 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include "ort_args.h"  // KArgs / JArgs, fill_args, localize / globalize, interact, pol_step
 #include "ort_core.h"
 #include "ort_fastpath.h"
 #include "ort_interact.h"
 #include "ort_material.h"
-#include "ort_sweep.h"  // KArgs, fill_args, localize / globalize, the derivative sweeps
 
 namespace ortk {
 
@@ -43,6 +46,12 @@ namespace ortk {
 #else
 #define ORT_ST(lhs, v) ((lhs) = (v))
 #endif
+// the same as the store policy of ort_args.h's store_ray / store_record
+struct StreamStore {
+  static __device__ inline __attribute__((always_inline)) void put(double& lhs, double v) {
+    ORT_ST(lhs, v);
+  }
+};
 
 
 constexpr int kBlock = 256;
@@ -155,21 +164,6 @@ __device__ inline double final_alpha(const KArgs& a, int lam, double w) {
     return ort::absorption_alpha(ort::material_k(cst(a.mats)[a.final_mat], a.coef, w), w);
   if constexpr ((FEAT & F_MONO) != 0) return cst(a.alpha_tab)[uniform_row(lam) * a.n_mat + a.final_mat];
   return tab(a.alpha_tab, a.n_lambda, a.n_mat, lam, a.final_mat);
-}
-
-// geometry ids this library implements (enum ort_geometry); the kernels turn any other
-// id into NaN rays plus ORT_STATUS_BAD_GEOMETRY
-__device__ inline bool known_geometry(int g) { return g >= ORT_GEOM_PLANE && g <= ORT_GEOM_NURBS; }
-// surfaces of the Newton schedule / statistics machinery (not plane, conic or NURBS)
-__device__ inline bool scheduled_geometry(int g) {
-  return g != ORT_GEOM_PLANE && g != ORT_GEOM_STANDARD && g != ORT_GEOM_NURBS;
-}
-
-// status bit of a normalisation-range error at surface s (zernike.py:234-246,
-// chebyshev.py:203-215: both raise ValueError in the reference)
-__device__ inline int range_bit(const ort_surface& s) {
-  return s.geometry == ORT_GEOM_CHEBYSHEV ? (int)ORT_STATUS_CHEBYSHEV_RANGE
-                                          : (int)ORT_STATUS_ZERNIKE_RANGE;
 }
 
 // Per-lane "the stop test passed at stop index k" bits over the 128-index window
@@ -450,38 +444,6 @@ __device__ inline __attribute__((always_inline)) double newton_distance(const KA
   return t;
 }
 
-// F_IA: the surface's interaction model after propagation / OPD / clipping
-// (standard_surface.py:225 -> interactions/*.py). unnorm tracks the reference's
-// rays.is_normalized flag, which only a thin lens clears (homogeneous.py:55-57).
-template <uint32_t FEAT>
-__device__ inline void interact(const KArgs& a, const ort_surface& s, ort::Ray& r,
-                                const ort_surface_optics& o, int lam, double wl,
-                                bool& unnorm) {
-  const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
-  const PD p = cst(a.coef) + s.ia_off;
-  if (s.interaction == ORT_IA_THIN_LENS) {
-    ort::thin_lens(r, p[0], o.n_pre, refl ? -o.n_pre : o.n_post);
-    unnorm = true;
-    return;
-  }
-  double nx, ny, nz;
-  ort::surface_normal<(FEAT & F_KM)>(s, s.radius, s.conic, cst(a.coef), cst(a.zern), kNoSeed,
-                                     r, nx, ny, nz);
-  if (s.interaction == ORT_IA_REFRACT_REFLECT) {
-    if (refl)
-      ort::reflect(r, nx, ny, nz);
-    else
-      ort::refract(r, nx, ny, nz, o.u);
-    return;
-  }
-  double w = wl;
-  if constexpr ((FEAT & F_WRAY) == 0) w = a.n_lambda == 1 ? cst(a.lambdas)[0] : a.lambdas[lam];
-  if (s.interaction == ORT_IA_PHASE)
-    ort::phase_interact(r, p, nx, ny, nz, o.n_pre, refl ? o.n_pre : o.n_post, refl, w);
-  else
-    ort::diffract(r, p, nx, ny, nz, o.n_pre, o.n_post, refl, w);
-}
-
 // Occupancy of the Newton kernels: the Zernike kernels (without freeform kinds) need
 // ~115 VGPRs (4 waves per SIMD); capped at 80 (6 waves, ~128 B scratch per lane) the TMA
 // forward runs 9% faster on the MI355X (334 -> 305 us per 1M-ray launch, rocprofv3; 5
@@ -617,46 +579,7 @@ __device__ inline int newton_decide(const ort_surface* surf, int32_t n_surf, int
 // in the order the kernels had them spelled out, so the kernels' code is unchanged: the
 // ray is filled and the intensity (whose exp is a branch) evaluated in place, between the
 // N and the opd store.
-// the caller's ray r_ld (kernels without F_GEN)
-__device__ inline void load_ray(const KArgs& a, int64_t r_ld, ort::Ray& r) {
-  r.x = a.in.x[r_ld];
-  r.y = a.in.y[r_ld];
-  r.z = a.in.z[r_ld];
-  r.L = a.in.L[r_ld];
-  r.M = a.in.M[r_ld];
-  r.N = a.in.N[r_ld];
-  r.i = a.in.i[r_ld];
-  r.opd = a.in.opd[r_ld];
-  r.att = 0.0;
-}
-
-// inten: the intensity to store instead of the ray's own (trace_closed_kernel's apodized one)
-__device__ inline void store_ray(const KArgs& a, int64_t rid, const ort::Ray& r,
-                                 const double* inten = nullptr) {
-  ORT_ST(a.out.x[rid], r.x);
-  ORT_ST(a.out.y[rid], r.y);
-  ORT_ST(a.out.z[rid], r.z);
-  ORT_ST(a.out.L[rid], r.L);
-  ORT_ST(a.out.M[rid], r.M);
-  ORT_ST(a.out.N[rid], r.N);
-  ORT_ST(a.out.i[rid], inten ? *inten : ort::intensity(r));
-  ORT_ST(a.out.opd[rid], r.opd);
-}
-
-// F_REC: ray rid's row of a recording surface (after globalize). apod: the pupil factor
-// the closed kernel multiplies into a recorded intensity (closed_surfaces)
-__device__ inline void store_record(const KArgs& a, const ort_surface& s, int64_t rid,
-                                    const ort::Ray& r, const double* apod = nullptr) {
-  double* base = a.rec + (int64_t)s.rec_slot * 8 * a.n_rays + rid;
-  ORT_ST(base[0 * a.n_rays], r.x);
-  ORT_ST(base[1 * a.n_rays], r.y);
-  ORT_ST(base[2 * a.n_rays], r.z);
-  ORT_ST(base[3 * a.n_rays], r.L);
-  ORT_ST(base[4 * a.n_rays], r.M);
-  ORT_ST(base[5 * a.n_rays], r.N);
-  ORT_ST(base[6 * a.n_rays], apod ? *apod * ort::intensity(r) : ort::intensity(r));
-  ORT_ST(base[7 * a.n_rays], r.opd);
-}
+// (load_ray, store_ray<StreamStore> and store_record<StreamStore> are ort_args.h's.)
 
 // F_TAPE: the ray as it arrives at a surface (global frame), rows 0..5 of the surface's
 // tape rows tp of this ray
@@ -778,7 +701,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
       ort::add_opd(r, t, n_pre);
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-      interact<FEAT>(a, s, r, o, lam, wl, unnorm);
+      interact<(FEAT & F_KM), (FEAT & F_WRAY) != 0>(a, s, r, o, lam, wl, unnorm);
     } else if constexpr (FAST) {
       // the closed kernel's fast surface step (closed_surfaces), the Newton surfaces with
       // the normal of their last evaluation
@@ -832,7 +755,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
     }
     globalize(a, s, r);
     if constexpr ((FEAT & F_REC) != 0) {
-      if ((s.flags & ORT_SURF_RECORD) && active) store_record(a, s, rid, r);
+      if ((s.flags & ORT_SURF_RECORD) && active) store_record<StreamStore>(a, s, rid, r);
     }
   }
   // real_ray_tracer.py:84-89: image-space propagate by the last surface's thickness
@@ -875,13 +798,13 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       if (bad) {
         ort::Ray rb = rf;
         rb.x = __builtin_nan("");
-        if (active) store_ray(a, rid, rb);
+        if (active) store_ray<StreamStore>(a, rid, rb);
         return;
       }
 #endif
       if (!bad) {
         if (fast_bits && active && a.status) atomicOr(a.status, fast_bits);
-        if (active) store_ray(a, rid, rf);
+        if (active) store_ray<StreamStore>(a, rid, rf);
         return;
       }
       redo = true;
@@ -962,28 +885,13 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       ort::add_opd(r, t, n_pre);
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-      interact<FEAT>(a, s, r, o, lam, wl, unnorm);
+      interact<(FEAT & F_KM), (FEAT & F_WRAY) != 0>(a, s, r, o, lam, wl, unnorm);
     } else if constexpr ((FEAT & F_POL) != 0) {
       // the generic step below with the normal and the direction before the interaction
       // kept for the polarization update (the ray's own operations are unchanged)
       to_intersection(a, s, r, t, alpha, n_pre);
       double nx = hnx, ny = hny, nz = hnz;
-      if (!hn)
-        ort::surface_normal<(FEAT & F_KM)>(s, s.radius, s.conic, cst(a.coef), cst(a.zern),
-                                           kNoSeed, r, nx, ny, nz);
-      const double k0x = r.L, k0y = r.M, k0z = r.N;
-      const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
-      if (refl)
-        ort::reflect(r, nx, ny, nz);
-      else
-        ort::refract(r, nx, ny, nz, u);
-      const ort_coating ct = cst(a.coat)[si];
-      double n1 = 1.0, n2 = 1.0;  // the coating's own materials at this wavelength
-      if (ct.kind == ORT_COAT_FRESNEL) {
-        n1 = tab(a.n_tab, a.n_lambda, a.n_mat, lam, ct.mat_pre);
-        n2 = tab(a.n_tab, a.n_lambda, a.n_mat, lam, ct.mat_post);
-      }
-      ort::pol_surface(pol, ct, refl, nx, ny, nz, k0x, k0y, k0z, r.L, r.M, r.N, n1, n2, r.i);
+      pol_step<(FEAT & F_KM)>(a, s, o, si, lam, r, pol, hn, nx, ny, nz);
     } else if constexpr ((FEAT & F_KM) != 0) {
       if (hn) {  // finish_surface with the normal of the last Newton evaluation
         to_intersection(a, s, r, t, alpha, n_pre);
@@ -1013,7 +921,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
     }
     globalize(a, s, r);
     if constexpr ((FEAT & F_REC) != 0) {
-      if ((s.flags & ORT_SURF_RECORD) && active) store_record(a, s, rid, r);
+      if ((s.flags & ORT_SURF_RECORD) && active) store_record<StreamStore>(a, s, rid, r);
     }
   }
   // real_ray_tracer.py:84-89: image-space propagate by the last surface's thickness
@@ -1031,7 +939,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
   if constexpr ((FEAT & F_POL) != 0) {
     // PolarizedRays.update_intensity per the mode, and the optional planes of P
     const double inten = ort::pol_intensity(pol, a.pol_mode, a.pol_ex, a.pol_ey, ort::intensity(r));
-    store_ray(a, rid, r, &inten);
+    store_ray<StreamStore>(a, rid, r, &inten);
     if (a.p_out) {
 #pragma unroll
       for (int e = 0; e < 9; ++e) {
@@ -1041,7 +949,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
     }
     return;
   }
-  store_ray(a, rid, r);
+  store_ray<StreamStore>(a, rid, r);
 }
 
 template <uint32_t FEAT>
@@ -1244,9 +1152,9 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     if constexpr ((FEAT & F_REC) != 0) {
       if ((s.flags & ORT_SURF_RECORD) && active) {
         if constexpr ((FEAT & F_GEN) != 0)
-          store_record(a, s, rid, r, a.apod ? &apod : nullptr);
+          store_record<StreamStore>(a, s, rid, r, a.apod ? &apod : nullptr);
         else
-          store_record(a, s, rid, r);
+          store_record<StreamStore>(a, s, rid, r);
       }
     }
   }
@@ -1339,7 +1247,7 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
 #endif
   if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(b, r, inten, active);
   if (!active) return;
-  store_ray(b, rid, r, &inten);
+  store_ray<StreamStore>(b, rid, r, &inten);
 }
 
 // Sum over the 64 lanes of a wave. With the whole wave active: DPP row operations
@@ -1370,52 +1278,6 @@ __device__ inline double wave_sum(double v) {
   }
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// ---------------------------------------------------------------------------------
-// Forward-mode VJP (ORT_VJP_UNROLLED): vjp_ray (ort_sweep.h) per lane; each block writes
-// its P sums (wave sums, then the block's four waves in order) to partial[block][P] and
-// vjp_reduce_kernel adds, per parameter, the blocks' sums in index order to grad: the
-// same bits run to run (no atomics).
-// ---------------------------------------------------------------------------------
-template <int P, uint32_t KM>
-__global__ __launch_bounds__(kBlock) void vjp_kernel(const KArgs a, const JArgs j) {
-  const int64_t rid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool active = rid < a.n_rays;
-  double acc[P];
-  vjp_ray<P, KM>(a, j, rid, active, acc);
-  __shared__ double part[kBlock / 64][P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) {
-    const double v = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < P) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) v += part[w][threadIdx.x];
-    j.partial[(int64_t)blockIdx.x * P + threadIdx.x] = v;
-  }
-}
-
-// One block per parameter k < P of the chunk: grad[p0 + k] += the blocks' partials summed
-// in a fixed order (strided per thread, wave sums, the four waves in order).
-template <int P>
-__global__ __launch_bounds__(kBlock) void vjp_reduce_kernel(const JArgs j, int64_t n_block) {
-  const int k = blockIdx.x;
-  if (j.p0 + k >= j.n_param) return;  // uniform
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < n_block; b += kBlock) v += j.partial[b * P + k];
-  v = wave_sum(v);
-  __shared__ double ws[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int w = 0; w < kBlock / 64; ++w) s += ws[w];
-    j.grad[j.p0 + k] += s;
-  }
 }
 
 // ---------------------------------------------------------------------------------
