@@ -62,6 +62,10 @@ namespace fast {
 #define ORT_CHK_UNIFORM(bad, cond) ::ort::fast::chk_uniform((bad), (cond))
 #endif
 
+// ORT_SEED_MAG_ONLY (A/B builds, tools/build_variant.py): of round 8's seeded reciprocals
+// the conic normal's magnitude alone -- the generated ray's norm keeps v_rcp -- the build
+// that priced one v_rcp_f64 (profiles/r08_closed_seeds.md)
+
 // The flag a sequence ORs its range failures into (the functions' class B): a per-lane
 // bool, or WaveFlag, the same flags of a whole wave as a mask (bit = lane). A loop that
 // carries a bool across uniform branches keeps it in a vector register and converts it
@@ -88,9 +92,18 @@ ORT_INLINE bool is_pos_zero(double v) {
 #endif
 }
 
-// sqrt(x) for 2^-767 <= x < inf (ort_core.h sqrt)
+// The square roots below are ort_core.h's Goldschmidt sequence: y = v_rsq(x) with relative
+// error e0, g = x y, h = y / 2, one coupled step r = 1/2 - h g, g += g r, h += h r, then two
+// residual corrections of g. With y = (1 + e0) / sqrt(x): r = 1/2 - (1 + e0)^2 / 2 =
+// -e0 - e0^2 / 2, so the refined h = (1 + e0)(1 - e0 - e0^2 / 2) / (2 sqrt(x)) =
+// (1 - 1.5 e0^2 + O(e0^3)) / (2 sqrt(x)) up to three roundings (2^-52 relative together).
+// The *_h forms hand that h out: 2 h is a reciprocal of the returned root g (g is sqrt(x)
+// rounded: 2^-53 more) with relative error |eh| <= 1.5 e0^2 + 2^-51, the seed of
+// shared_div_seeded below. The root itself is computed exactly as before.
+
+// sqrt(x) for 2^-767 <= x < inf (ort_core.h sqrt); h: see above (host: unused, 0)
 template <class B>
-ORT_INLINE double sqrt(double x, B& bad) {
+ORT_INLINE double sqrt_h(double x, B& bad, double& h_out) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y;
@@ -103,17 +116,24 @@ ORT_INLINE double sqrt(double x, B& bad) {
   d = fma(-g, g, x);
   g = fma(d, h, g);
   ORT_CHK(bad, !(x >= 0x1p-767));  // +inf gives NaN: left to state_ok
+  h_out = h;
   return g;
 #else
   (void)bad;
+  h_out = 0.0;
   return ::sqrt(x);
 #endif
+}
+template <class B>
+ORT_INLINE double sqrt(double x, B& bad) {
+  double h;
+  return sqrt_h(x, bad, h);
 }
 
 // sqrt(x) where x >= 1 unless NaN (sums of squares plus 1): only the upper bound could
 // fail, and +inf / NaN give NaN, which state_ok catches: no test
 template <class B>
-ORT_INLINE double sqrt_ge1(double x, B& bad) {
+ORT_INLINE double sqrt_ge1_h(double x, B& bad, double& h_out) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y;
@@ -126,11 +146,18 @@ ORT_INLINE double sqrt_ge1(double x, B& bad) {
   d = fma(-g, g, x);
   g = fma(d, h, g);
   (void)bad;
+  h_out = h;
   return g;
 #else
   (void)bad;
+  h_out = 0.0;
   return ::sqrt(x);
 #endif
+}
+template <class B>
+ORT_INLINE double sqrt_ge1(double x, B& bad) {
+  double h;
+  return sqrt_ge1_h(x, bad, h);
 }
 
 template <class B>
@@ -180,6 +207,47 @@ ORT_INLINE SharedDiv shared_div_ge1(double b, B& bad) {
   d.y = y;
 #else
   (void)bad;
+  d.y = 0.0;
+#endif
+  return d;
+}
+
+// shared_div / shared_div_ge1 from a seed y0 = (1 + es) / b instead of v_rcp(b): ONE Newton
+// step e = fma(-b, y0, 1) = -es (exact up to its rounding), y = fma(y0, e, y0) =
+// (1 - es^2) / b rounded. v_rcp's own error e1 leaves the unseeded forms at e1^2 after their
+// first step and e1^4 after the second; a seed with |es| <= 1.5 e0^2 + 2^-51 (sqrt_h's
+// 2 h) stands where that first step ends, and the one step lands at es^2 ~ 2.25 e0^4 --
+// for e0 <= 2^-20 under 2^-78, far below the 2^-53 of y's own rounding, as e1^4 is. The
+// quotient sequence then rounds the same real a / b from a reciprocal of the same
+// accuracy. Range tests: the unseeded forms', unchanged.
+// A non-finite or zero seed (x = 0, inf or NaN under the root) gives a NaN reciprocal and
+// NaN quotients where v_rcp gave inf / 0 / NaN: non-finite either way, for state_ok.
+template <class B>
+ORT_INLINE SharedDiv shared_div_seeded(double b, double y0, B& bad) {
+  SharedDiv d;
+  d.b = b;
+  d.ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double e = fma(-b, y0, 1.0);
+  d.y = fma(y0, e, y0);
+  ORT_CHK(bad, !(::fabs(b) <= 0x1p300));  // as shared_div
+#else
+  (void)bad;
+  (void)y0;
+  d.y = 0.0;
+#endif
+  return d;
+}
+// divisor in [1, inf) unless NaN: no test (shared_div_ge1)
+ORT_INLINE SharedDiv shared_div_ge1_seeded(double b, double y0) {
+  SharedDiv d;
+  d.b = b;
+  d.ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double e = fma(-b, y0, 1.0);
+  d.y = fma(y0, e, y0);
+#else
+  (void)y0;
   d.y = 0.0;
 #endif
   return d;
@@ -259,9 +327,18 @@ ORT_INLINE Ray generate_ray(const ort_segment& s, double px, double py,
   }
   const double z1 = s.epl;
   const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
+#ifndef ORT_SEED_MAG_ONLY
+  // the norm's reciprocal seeded by its own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after
+  // the step (shared_div_seeded)
+  double hm;
+  const double mag = sqrt_h(dx * dx + dy * dy + dz * dz, bad, hm);
+  ORT_CHK(bad, (mag < 1e-9));  // the (0, 0, 1) branch of ray_generator.py:82-89
+  const SharedDiv dm = shared_div_seeded(mag, 2.0 * hm, bad);
+#else
   const double mag = sqrt(dx * dx + dy * dy + dz * dz, bad);
   ORT_CHK(bad, (mag < 1e-9));  // the (0, 0, 1) branch of ray_generator.py:82-89
   const SharedDiv dm = shared_div(mag, bad);
+#endif
   // mag > 0: quot_pos is exact for zero numerators of either sign
   ORT_CHK(bad, !((num_ok(dx) || dx == 0.0) && (num_ok(dy) || dy == 0.0) &&
                  (num_ok(dz) || dz == 0.0)));
@@ -403,8 +480,10 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, doubl
   const SharedDiv dd = shared_div(denom, bad);
   const double dfdx = sdiv0(x, dd, bad);
   const double dfdy = sdiv0(y, dd, bad);
-  const double mag = sqrt_ge1(dfdx * dfdx + dfdy * dfdy + 1.0, bad);
-  const SharedDiv dm = shared_div_ge1(mag, bad);
+  // 1 / mag seeded by 2 h of mag's own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after the step
+  double hm;
+  const double mag = sqrt_ge1_h(dfdx * dfdx + dfdy * dfdy + 1.0, bad, hm);
+  const SharedDiv dm = shared_div_ge1_seeded(mag, 2.0 * hm);
   // dfdx = x / denom with x checked (|x| in [2^-300, 2^300] or +0) and |denom| <= 2^300:
   // |dfdx| >= 2^-600 or +-0, and |dfdx| <= mag -- in range for the positive divisor
   // mag, zeros of either sign included (quot_pos): no check left to make
