@@ -1,0 +1,124 @@
+"""The Python call layer of the two C ABIs: the argument structs of include/optiland_rt.h
+(and of include/optiland_host.h, which takes the same ones) built from tensors, once, for
+raytrace.py, autodiff.py, ops.py, host.py, polarization.py and distributed.py -- the Python
+counterpart of csrc/ort_args.h, which reads these structs for both libraries. Flat
+functions over _native's ctypes structs; no torch ops and no launches here.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, _native
+
+try:
+    import torch
+except ImportError:  # pragma: no cover
+    torch = None
+
+
+def addr(t):
+    """The address of a tensor's or a numpy array's first element for a c_void_p field or
+    argument; None (NULL) for None."""
+    if t is None:
+        return None
+    return t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data
+
+
+def rays_struct(ts):
+    """ort_rays of 8 tensors (x, y, z, L, M, N, i, opd); None: a NULL field."""
+    return _native.ort_rays(*(addr(t) for t in ts))
+
+
+def _batch(n, seg_len, group_len, seg, pupil_per_ray, apod):
+    if n == 0:
+        # an empty batch: no ray reads the lengths, and the C front end (ort_args.h
+        # fill_args) wants both >= 1. With rays they go as given, so that it still refuses
+        # a caller's zero instead of indexing the segments by it.
+        seg_len, group_len = max(seg_len, 1), max(group_len, 1)
+    n_seg = 0 if seg is None else seg.numel() // _abi.SEGMENT.itemsize
+    return _native.ort_batch(n, seg_len, group_len, n_seg, int(pupil_per_ray), addr(seg), None,
+                             addr(apod))
+
+
+def pupil_batch(n, seg_len, group_len, seg, pupil_per_ray=False, apod=None):
+    """ort_batch of rays generated from pupil samples: ray r belongs to segment r // seg_len
+    of `seg` (SEGMENT records as a uint8 tensor), Newton groups of group_len rays; apod: the
+    APODIZATION record (uint8 tensor) or None."""
+    return _batch(n, seg_len, group_len, seg, pupil_per_ray, apod)
+
+
+def resident_batch(n, group_len=None, seg=None, seg_len=None):
+    """ort_batch of resident rays: one segment and one Newton group of all n unless given
+    (seg / seg_len: per-segment wavelength rows, as pupil_batch). Per-ray wavelengths go
+    into its `w` field (per_ray_wavelengths)."""
+    return _batch(n, seg_len or max(n, 1), group_len or max(n, 1), seg, False, None)
+
+
+def per_ray_wavelengths(table, w, n, device, validate):
+    """ort_batch.w: `w` as n contiguous float64 wavelengths on `device` (one value: expanded;
+    already so: the same memory, no copy). The caller keeps the result alive until its
+    launches are ordered on the stream.
+
+    validate: refuse wavelengths outside the Abbe model's 0.380-0.750 um when the lens has
+    such a material, as the reference does before it uses any index (abbe.py:47-48; the
+    device would only give NaN). That reads `w` -- a device synchronisation -- so the
+    forward traces validate and the VJPs do not: a backward's `w` is the one its forward
+    checked. This is the one intended difference between the call sites."""
+    w = w.detach().to(device=device, dtype=torch.float64).reshape(-1)
+    w = w.expand(n).contiguous() if w.numel() == 1 else w.contiguous()
+    if w.numel() != n:
+        raise ValueError("rays.w must hold one wavelength per ray")
+    mt = table.mat_table
+    if validate and mt is not None and np.any(mt["kind"] == _abi.MAT_ABBE):
+        if bool(((w < 0.380) | (w > 0.750)).any()):
+            raise ValueError("Wavelength out of range for this model.")
+    return w
+
+
+def vjp_params(table, n_param, mode, tabs, need, grad_init, tape=None, primal=None, rms=None):
+    """ort_vjp_params without its workspace (attach_vjp_workspace). tabs: (zern_param,
+    surf_tangent, final_tangent) tensors or None; need: slot_need or None; grad_init: the
+    gradient is overwritten; tape / primal: the adjoint tape the forward wrote and its 8
+    outputs (the device's adjoint mode); rms: (stats[5], g[1]) of an rms spot size folded
+    into the x, y cotangents. n_mono is the adjoint mode's: no unrolled path of either
+    library reads it (ort_args.h vjp_fill_unrolled, ort_api.hip adj_layout)."""
+    from .ops import mono_slot_count
+
+    zp, st, ft = tabs
+    p = _native.ort_vjp_params(int(n_param), int(mode), addr(zp), addr(st), addr(ft),
+                               0 if zp is None else int(zp.numel()), int(bool(grad_init)),
+                               None, 0, addr(need))
+    if mode == _abi.VJP_ADJOINT:
+        p.n_mono = mono_slot_count(table, zp)
+    if tape is not None:
+        p.tape, p.primal = addr(tape), rays_struct(primal)
+    if rms is not None:
+        p.rms_stats, p.rms_grad = addr(rms[0]), addr(rms[1])
+    return p
+
+
+_WORKSPACES: dict = {}
+
+
+def workspace(pool, device, nbytes):
+    """Scratch bytes on `device`, grown on demand and reused by every later call of the same
+    pool (at least 8 bytes, so never a NULL address). One pool per op that owns a buffer:
+    "pupil_vjp", "seq_vjp", "rms"."""
+    ws = _WORKSPACES.get((pool, device))
+    if ws is None or ws.numel() < nbytes:
+        _WORKSPACES.pop((pool, device), None)
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+        _WORKSPACES[(pool, device)] = ws
+    return ws
+
+
+def attach_vjp_workspace(lib, lens_c, batch, params, pool, device):
+    """Give `params` the device workspace its VJP call needs (ort_vjp_workspace_size; both
+    modes take one), from `pool`."""
+    size = lib.ort_vjp_workspace_size(C.byref(lens_c), C.byref(batch), C.byref(params))
+    _native.check(int(size) if size < 0 else 0, "ort_vjp_workspace_size")
+    ws = workspace(pool, device, size)
+    params.workspace, params.workspace_size = ws.data_ptr(), ws.numel()

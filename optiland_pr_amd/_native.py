@@ -160,246 +160,128 @@ class ort_wavefront_ref(C.Structure):
     _fields_ += [("tilt", C.c_int32), ("reserved", C.c_int32)]
 
 
-EXPORTS = ("ort_abi_version", "ort_trace_sequential", "ort_trace_pupil", "ort_trace_pupil_vjp",
-           "ort_trace_sequential_vjp",
-           "ort_vjp_workspace_size", "ort_vjp_tape_size", "ort_generate_pupil", "ort_newton_fixup",
-           "ort_surface_sag_normal", "ort_surface_distance", "ort_generate_rays",
-           "ort_material_nk", "ort_spot_workspace_size", "ort_spot_stats", "ort_trace_spot", "ort_spot_partials",
-           "ort_rms_spot_workspace_size", "ort_rms_spot", "ort_rms_spot_vjp",
-           "ort_wavefront_workspace_size", "ort_wavefront_opd", "ort_patch_zernike",
-           "ort_patch_zernike_ptrs", "ort_newton_finish", "ort_adam_patch_zernike",
-           "ort_rms_finish", "ort_newton_finish_rms", "ort_huygens_workspace_size",
-           "ort_huygens_psf", "ort_irradiance_workspace_size", "ort_irradiance_bin",
-           "ort_irradiance_bin_vjp", "ort_trace_pupil_polarized",
-           "ort_trace_sequential_polarized")
+# The prototypes of both libraries, name -> (restype, argtypes), as their headers declare
+# them: every exported symbol is a key, so none can be exported without its argument types.
+PTR, I32, I64, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+LENS, RAYS, BATCH, OPTIONS = (C.POINTER(s) for s in (ort_lens, ort_rays, ort_batch, ort_options))
+VJP, POL, SPOT = (C.POINTER(s) for s in (ort_vjp_params, ort_polarization, ort_spot_layout))
 
-_lib = None
+DEVICE_PROTOTYPES = {
+    "ort_abi_version": (C.c_int, []),
+    "ort_trace_sequential": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR, PTR, PTR]),
+    "ort_trace_pupil": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR, PTR, PTR]),
+    "ort_trace_pupil_vjp": (C.c_int, [LENS, PTR, PTR, BATCH, OPTIONS, VJP, RAYS, PTR, PTR]),
+    "ort_trace_sequential_vjp": (C.c_int, [LENS, RAYS, BATCH, OPTIONS, VJP, RAYS, PTR, PTR, PTR,
+                                           RAYS, PTR]),
+    "ort_vjp_workspace_size": (I64, [LENS, BATCH, VJP]),
+    "ort_vjp_tape_size": (I64, [LENS, BATCH]),
+    "ort_generate_pupil": (C.c_int, [C.POINTER(ort_pupil), PTR, PTR, PTR]),
+    "ort_newton_fixup": (C.c_int, [LENS, I64, PTR, I32, PTR, PTR, PTR, PTR, PTR, PTR]),
+    "ort_surface_sag_normal": (C.c_int, [LENS, I32, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR,
+                                         PTR]),
+    "ort_surface_distance": (C.c_int, [LENS, I32, RAYS, I64, OPTIONS, PTR, PTR, PTR, PTR]),
+    "ort_generate_rays": (C.c_int, [PTR, PTR, RAYS, BATCH, PTR]),
+    "ort_material_nk": (C.c_int, [LENS, I32, PTR, I64, PTR, PTR, PTR]),
+    "ort_spot_workspace_size": (I64, [SPOT]),
+    "ort_spot_stats": (C.c_int, [RAYS, SPOT, PTR, I64, PTR, PTR]),
+    "ort_trace_spot": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, SPOT, PTR, I64, PTR,
+                                 PTR]),
+    "ort_spot_partials": (C.c_int, [RAYS, SPOT, I32, PTR, PTR, I64, PTR, PTR]),
+    "ort_rms_spot_workspace_size": (I64, [I64]),
+    "ort_rms_spot": (C.c_int, [PTR, PTR, I64, PTR, I64, PTR, PTR, PTR]),
+    "ort_rms_spot_vjp": (C.c_int, [PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR]),
+    "ort_wavefront_workspace_size": (I64, [I64]),
+    "ort_wavefront_opd": (C.c_int, [RAYS, PTR, PTR, I64, C.POINTER(ort_wavefront_ref), PTR, PTR,
+                                    PTR, PTR, PTR, I64, PTR, PTR]),
+    "ort_patch_zernike": (C.c_int, [LENS, PTR, PTR, I64, PTR]),
+    "ort_patch_zernike_ptrs": (C.c_int, [LENS, PTR, PTR, I64, PTR]),
+    "ort_newton_finish": (C.c_int, [LENS, I64, PTR, I32, I32, PTR, PTR, PTR, PTR, PTR, PTR]),
+    "ort_adam_patch_zernike": (C.c_int, [LENS, C.POINTER(ort_adam_params), PTR]),
+    "ort_rms_finish": (C.c_int, [PTR, I64, PTR, PTR, PTR]),
+    "ort_newton_finish_rms": (C.c_int, [LENS, I64, PTR, I32, I32, PTR, PTR, PTR, PTR, PTR, PTR,
+                                        I64, PTR, PTR, PTR]),
+    "ort_huygens_workspace_size": (I64, [I64, I64]),
+    "ort_huygens_psf": (C.c_int, [PTR, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR, I64, F64, F64,
+                                  PTR, PTR, I64, PTR]),
+    "ort_irradiance_workspace_size": (I64, [I64, I64]),
+    "ort_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64, PTR, PTR,
+                                     I64, PTR]),
+    "ort_irradiance_bin_vjp": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, F64, PTR, PTR,
+                                         PTR, PTR, PTR]),
+    "ort_trace_pupil_polarized": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR, PTR,
+                                            POL, PTR]),
+    "ort_trace_sequential_polarized": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR, PTR,
+                                                 POL, PTR]),
+}
+
+HOST_PROTOTYPES = {
+    "ort_host_abi_version": (C.c_int, []),
+    "ort_host_trace_sequential": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR, PTR]),
+    "ort_host_trace_sequential_vjp": (C.c_int, [LENS, RAYS, BATCH, OPTIONS, VJP, RAYS, PTR, PTR,
+                                                PTR, RAYS]),
+    "ort_host_trace_pupil": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR]),
+    "ort_host_trace_pupil_vjp": (C.c_int, [LENS, PTR, PTR, BATCH, OPTIONS, VJP, RAYS, PTR]),
+    "ort_host_rms_spot": (C.c_int, [PTR, PTR, I64, PTR, PTR]),
+    "ort_host_rms_spot_vjp": (C.c_int, [PTR, PTR, I64, PTR, PTR, PTR, PTR]),
+    "ort_host_set_threads": (None, [I32]),
+    "ort_host_huygens_psf": (C.c_int, [PTR, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR, I64, F64,
+                                       F64, PTR]),
+    "ort_host_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64,
+                                          PTR]),
+    "ort_host_irradiance_bin_vjp": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, F64, PTR,
+                                              PTR, PTR, PTR]),
+    "ort_host_trace_pupil_polarized": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR,
+                                                 PTR, POL]),
+    "ort_host_trace_sequential_polarized": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR,
+                                                      PTR, PTR, POL]),
+    "ort_host_generate_rays": (C.c_int, [PTR, PTR, RAYS, BATCH]),
+}
+
+EXPORTS = tuple(DEVICE_PROTOTYPES)
+HOST_EXPORTS = tuple(HOST_PROTOTYPES)
+HOST_ABI_VERSION = 3  # include/optiland_host.h ORT_HOST_ABI_VERSION
 
 
 class NativeLibraryError(RuntimeError):
     pass
 
 
-def load(path: str | None = None):
-    """Load liboptiland_rt.so (raises NativeLibraryError when it is not built)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    # ORT_LIB_PATH: load an alternative build (A/B timing of kernel variants)
-    p = path or os.environ.get("ORT_LIB_PATH") or LIB_PATH
-    if not os.path.exists(p):
-        raise NativeLibraryError(
-            f"{p} is missing: build the HIP extension first "
-            "(python -m optiland_pr_amd.build or __graft_entry__.build())")
-    lib = C.CDLL(p)
-    lib.ort_abi_version.restype = C.c_int
-    lib.ort_abi_version.argtypes = []
-    P = C.POINTER
-    lib.ort_trace_sequential.restype = C.c_int
-    lib.ort_trace_sequential.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays), P(ort_batch),
-                                         P(ort_options), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]
-    lib.ort_trace_pupil.restype = C.c_int
-    lib.ort_trace_pupil.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_rays),
-                                    P(ort_batch), P(ort_options), C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-    lib.ort_trace_pupil_vjp.restype = C.c_int
-    lib.ort_trace_pupil_vjp.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_batch),
-                                        P(ort_options), P(ort_vjp_params), P(ort_rays),
-                                        C.c_void_p, C.c_void_p]
-    lib.ort_trace_sequential_vjp.restype = C.c_int
-    lib.ort_trace_sequential_vjp.argtypes = [P(ort_lens), P(ort_rays), P(ort_batch),
-                                             P(ort_options), P(ort_vjp_params), P(ort_rays),
-                                             C.c_void_p, C.c_void_p, C.c_void_p, P(ort_rays),
-                                             C.c_void_p]
-    lib.ort_vjp_tape_size.restype = C.c_int64
-    lib.ort_vjp_tape_size.argtypes = [P(ort_lens), P(ort_batch)]
-    lib.ort_vjp_workspace_size.restype = C.c_int64
-    lib.ort_vjp_workspace_size.argtypes = [P(ort_lens), P(ort_batch), P(ort_vjp_params)]
-    lib.ort_patch_zernike.restype = C.c_int
-    lib.ort_patch_zernike.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, C.c_int64,
-                                      C.c_void_p]
-    lib.ort_rms_finish.restype = C.c_int
-    lib.ort_rms_finish.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_adam_patch_zernike.restype = C.c_int
-    lib.ort_adam_patch_zernike.argtypes = [P(ort_lens), P(ort_adam_params), C.c_void_p]
-    lib.ort_patch_zernike_ptrs.restype = C.c_int
-    lib.ort_patch_zernike_ptrs.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, C.c_int64,
-                                           C.c_void_p]
-    lib.ort_newton_finish.restype = C.c_int
-    lib.ort_newton_finish.argtypes = [P(ort_lens), C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]
-    lib.ort_newton_finish_rms.restype = C.c_int
-    lib.ort_newton_finish_rms.argtypes = [P(ort_lens), C.c_int64, C.c_void_p, C.c_int32,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_surface_sag_normal.restype = C.c_int
-    lib.ort_surface_sag_normal.argtypes = [P(ort_lens), C.c_int32, C.c_void_p, C.c_void_p,
-                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_surface_distance.restype = C.c_int
-    lib.ort_surface_distance.argtypes = [P(ort_lens), C.c_int32, P(ort_rays), C.c_int64,
-                                         P(ort_options), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]
-    lib.ort_newton_fixup.restype = C.c_int
-    lib.ort_newton_fixup.argtypes = [P(ort_lens), C.c_int64, C.c_void_p, C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]
-    lib.ort_generate_pupil.restype = C.c_int
-    lib.ort_generate_pupil.argtypes = [P(ort_pupil), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_material_nk.restype = C.c_int
-    lib.ort_material_nk.argtypes = [P(ort_lens), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-    lib.ort_generate_rays.restype = C.c_int
-    lib.ort_generate_rays.argtypes = [C.c_void_p, C.c_void_p, P(ort_rays), P(ort_batch),
-                                      C.c_void_p]
-    lib.ort_spot_workspace_size.restype = C.c_int64
-    lib.ort_spot_workspace_size.argtypes = [P(ort_spot_layout)]
-    lib.ort_spot_stats.restype = C.c_int
-    lib.ort_spot_stats.argtypes = [P(ort_rays), P(ort_spot_layout), C.c_void_p, C.c_int64,
-                                   C.c_void_p, C.c_void_p]
-    lib.ort_trace_spot.restype = C.c_int
-    lib.ort_trace_spot.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_rays),
-                                   P(ort_batch), P(ort_options), C.c_void_p,
-                                   P(ort_spot_layout), C.c_void_p, C.c_int64, C.c_void_p,
-                                   C.c_void_p]
-    lib.ort_spot_partials.restype = C.c_int
-    lib.ort_spot_partials.argtypes = [P(ort_rays), P(ort_spot_layout), C.c_int32, C.c_void_p,
-                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.ort_rms_spot_workspace_size.restype = C.c_int64
-    lib.ort_rms_spot_workspace_size.argtypes = [C.c_int64]
-    lib.ort_rms_spot.restype = C.c_int
-    lib.ort_rms_spot.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                 C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_rms_spot_vjp.restype = C.c_int
-    lib.ort_rms_spot_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_wavefront_workspace_size.restype = C.c_int64
-    lib.ort_wavefront_workspace_size.argtypes = [C.c_int64]
-    lib.ort_wavefront_opd.restype = C.c_int
-    lib.ort_wavefront_opd.argtypes = [P(ort_rays), C.c_void_p, C.c_void_p, C.c_int64,
-                                      P(ort_wavefront_ref), C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                      C.c_void_p, C.c_void_p]
-    lib.ort_huygens_workspace_size.restype = C.c_int64
-    lib.ort_huygens_workspace_size.argtypes = [C.c_int64, C.c_int64]
-    lib.ort_huygens_psf.restype = C.c_int
-    lib.ort_huygens_psf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.c_void_p]
-    lib.ort_irradiance_workspace_size.restype = C.c_int64
-    lib.ort_irradiance_workspace_size.argtypes = [C.c_int64, C.c_int64]
-    lib.ort_irradiance_bin.restype = C.c_int
-    lib.ort_irradiance_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
-                                       C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.c_void_p]
-    lib.ort_irradiance_bin_vjp.restype = C.c_int
-    lib.ort_irradiance_bin_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                           C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-    lib.ort_trace_pupil_polarized.restype = C.c_int
-    lib.ort_trace_pupil_polarized.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_rays),
-                                              P(ort_batch), P(ort_options), C.c_void_p,
-                                              C.c_void_p, C.c_void_p, P(ort_polarization),
-                                              C.c_void_p]
-    lib.ort_trace_sequential_polarized.restype = C.c_int
-    lib.ort_trace_sequential_polarized.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays),
-                                                   P(ort_batch), P(ort_options), C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, P(ort_polarization),
-                                                   C.c_void_p]
-    v = lib.ort_abi_version()
-    if v != _abi.ABI_VERSION:
-        raise NativeLibraryError(f"ABI version mismatch: library {v}, host {_abi.ABI_VERSION}")
-    if path is None:
-        _lib = lib
-    return lib
+_loaded: dict = {}  # default path -> the library loaded from it (or from its override)
 
 
-HOST_EXPORTS = ("ort_host_abi_version", "ort_host_trace_sequential",
-                "ort_host_trace_sequential_vjp", "ort_host_trace_pupil", "ort_host_trace_pupil_vjp",
-                "ort_host_rms_spot", "ort_host_rms_spot_vjp", "ort_host_set_threads",
-                "ort_host_huygens_psf", "ort_host_irradiance_bin",
-                "ort_host_irradiance_bin_vjp", "ort_host_trace_pupil_polarized",
-                "ort_host_trace_sequential_polarized", "ort_host_generate_rays")
-HOST_ABI_VERSION = 3  # include/optiland_host.h ORT_HOST_ABI_VERSION
-
-_host = None
-
-
-def load_host(path: str | None = None):
-    """Load liboptiland_host.so (raises NativeLibraryError when it is not built)."""
-    global _host
-    if _host is not None and path is None:
-        return _host
-    p = path or os.environ.get("ORT_HOST_LIB_PATH") or HOST_LIB_PATH
+def _load(path, env_var, default_path, table, version_symbol, expected, what):
+    """The library at `path`, else at $env_var, else at default_path, with every prototype
+    of `table` set and its ABI version checked; only the default lookup is cached."""
+    if path is None and default_path in _loaded:
+        return _loaded[default_path]
+    p = path or os.environ.get(env_var) or default_path
     if not os.path.exists(p):
         raise NativeLibraryError(
             f"{p} is missing: build the native libraries first "
             "(python -m optiland_pr_amd.build or __graft_entry__.build())")
     lib = C.CDLL(p)
-    P = C.POINTER
-    lib.ort_host_abi_version.restype = C.c_int
-    lib.ort_host_abi_version.argtypes = []
-    lib.ort_host_trace_sequential.restype = C.c_int
-    lib.ort_host_trace_sequential.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays),
-                                              P(ort_batch), P(ort_options), C.c_void_p,
-                                              C.c_void_p, C.c_void_p]
-    lib.ort_host_trace_sequential_vjp.restype = C.c_int
-    lib.ort_host_trace_sequential_vjp.argtypes = [P(ort_lens), P(ort_rays), P(ort_batch),
-                                                  P(ort_options), P(ort_vjp_params),
-                                                  P(ort_rays), C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, P(ort_rays)]
-    lib.ort_host_trace_pupil.restype = C.c_int
-    lib.ort_host_trace_pupil.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_rays),
-                                         P(ort_batch), P(ort_options), C.c_void_p, C.c_void_p]
-    lib.ort_host_trace_pupil_vjp.restype = C.c_int
-    lib.ort_host_trace_pupil_vjp.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p, P(ort_batch),
-                                             P(ort_options), P(ort_vjp_params), P(ort_rays),
-                                             C.c_void_p]
-    lib.ort_host_rms_spot.restype = C.c_int
-    lib.ort_host_rms_spot.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.ort_host_rms_spot_vjp.restype = C.c_int
-    lib.ort_host_rms_spot_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ort_host_set_threads.restype = None
-    lib.ort_host_set_threads.argtypes = [C.c_int32]
-    lib.ort_host_huygens_psf.restype = C.c_int
-    lib.ort_host_huygens_psf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_int64, C.c_double, C.c_double,
-                                         C.c_void_p]
-    lib.ort_host_irradiance_bin.restype = C.c_int
-    lib.ort_host_irradiance_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                            C.c_int32, C.c_double, C.c_void_p]
-    lib.ort_host_irradiance_bin_vjp.restype = C.c_int
-    lib.ort_host_irradiance_bin_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p]
-    lib.ort_host_trace_pupil_polarized.restype = C.c_int
-    lib.ort_host_trace_pupil_polarized.argtypes = [P(ort_lens), C.c_void_p, C.c_void_p,
-                                                   P(ort_rays), P(ort_batch), P(ort_options),
-                                                   C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   P(ort_polarization)]
-    lib.ort_host_trace_sequential_polarized.restype = C.c_int
-    lib.ort_host_trace_sequential_polarized.argtypes = [P(ort_lens), P(ort_rays), P(ort_rays),
-                                                        P(ort_batch), P(ort_options), C.c_void_p,
-                                                        C.c_void_p, C.c_void_p,
-                                                        P(ort_polarization)]
-    lib.ort_host_generate_rays.restype = C.c_int
-    lib.ort_host_generate_rays.argtypes = [C.c_void_p, C.c_void_p, P(ort_rays), P(ort_batch)]
-    v = lib.ort_host_abi_version()
-    if v != HOST_ABI_VERSION:
-        raise NativeLibraryError(f"host ABI version mismatch: library {v}, host {HOST_ABI_VERSION}")
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    v = getattr(lib, version_symbol)()
+    if v != expected:
+        raise NativeLibraryError(f"{what} version mismatch: library {v}, host {expected}")
     if path is None:
-        _host = lib
+        _loaded[default_path] = lib
     return lib
+
+
+def load(path: str | None = None):
+    """Load liboptiland_rt.so (raises NativeLibraryError when it is not built).
+    ORT_LIB_PATH: load an alternative build (A/B timing of kernel variants)."""
+    return _load(path, "ORT_LIB_PATH", LIB_PATH, DEVICE_PROTOTYPES, "ort_abi_version",
+                 _abi.ABI_VERSION, "ABI")
+
+
+def load_host(path: str | None = None):
+    """Load liboptiland_host.so (raises NativeLibraryError when it is not built)."""
+    return _load(path, "ORT_HOST_LIB_PATH", HOST_LIB_PATH, HOST_PROTOTYPES,
+                 "ort_host_abi_version", HOST_ABI_VERSION, "host ABI")
 
 
 def check(rc: int, what: str):

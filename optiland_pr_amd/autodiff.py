@@ -38,7 +38,8 @@ import os
 
 import numpy as np
 
-from . import _abi, _native
+from . import _abi, _calls, _native
+from ._calls import addr
 
 try:
     import torch
@@ -177,8 +178,6 @@ def schedule_for_mode(table, sched_t, hint=None):
     return sched_t.cpu()
 
 
-_WORKSPACE = {}
-
 # the forward of a differentiable Newton-lens trace writes the adjoint tape (F_TAPE), so
 # the backward skips its re-trace; ORT_TAPED_FORWARD=0 keeps the re-trace (A/B checks)
 TAPED_FORWARD = os.environ.get("ORT_TAPED_FORWARD", "1") != "0"
@@ -188,68 +187,39 @@ TAPED_FORWARD = os.environ.get("ORT_TAPED_FORWARD", "1") != "0"
 VJP_EVENTS = None
 
 
-def _workspace(device, nbytes):
-    """Device scratch for the adjoint VJP, grown on demand and reused (per device)."""
-    ws = _WORKSPACE.get(device)
-    if ws is None or ws.numel() < nbytes:
-        _WORKSPACE.pop(device, None)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _WORKSPACE[device] = ws
-    return ws
-
-
 def vjp(dlens, seg_dev, px, py, n, seg_len, sched_dev, tables, n_param, cot, grad,
         pupil_per_ray=False, mode=None, tape=None, primal=None, overwrite=False, rms=None):
     """grad += J^T cot through ort_trace_pupil_vjp (overwrite: grad = J^T cot, grad need
     not be initialised). tables: device tensors (zern_param, surf_tangent,
     final_tangent), each possibly None; cot: 8 tensors / None; rms: (stats[5], g[1]) of an
     rms spot size of the outputs, folded into the x, y cotangent load (adjoint mode)."""
-    from .raytrace import _ptr, _stream_handle
+    from .ops import _check_differentiable
+    from .raytrace import _stream_handle
 
-    if np.any(dlens.table.surfaces["geometry"] == _abi.GEOM_GRID_SAG):
-        raise NotImplementedError("autograd through grid-sag surfaces is not implemented by "
-                                  "the trace core (no derivative kernels)")
+    _check_differentiable(dlens.table)
     mode = vjp_mode(dlens.table) if mode is None else mode
     if has_interactions(dlens.table) and mode != _abi.VJP_UNROLLED:
         raise NotImplementedError("thin-lens, phase and grating surfaces are differentiated "
                                   "by the forward-mode VJP only (ORT_VJP_UNROLLED)")
+    if rms is not None and mode != _abi.VJP_ADJOINT:
+        raise ValueError("vjp: the rms cotangent fold is the adjoint mode's")
     lib = _native.load()
-    n_seg = seg_dev.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n, seg_len, n, n_seg, int(pupil_per_ray), seg_dev.data_ptr())
-    batch.apod = None if dlens.apod is None else dlens.apod.data_ptr()
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0,
-                              None if sched_dev is None else sched_dev.data_ptr())
-    zp, st, ft = tables[:3]
+    batch = _calls.pupil_batch(n, seg_len, n, seg_dev, pupil_per_ray, dlens.apod)
+    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, addr(sched_dev))
     need = tables[3] if len(tables) > 3 else None  # ort_vjp_params.slot_need (resident)
-    params = _native.ort_vjp_params(int(n_param), int(mode), _ptr(zp).value, _ptr(st).value,
-                                    _ptr(ft).value, 0 if zp is None else int(zp.numel()),
-                                    int(bool(overwrite)), None, 0, _ptr(need).value)
-    if mode == _abi.VJP_ADJOINT:
-        from .ops import mono_slot_count
-
-        params.n_mono = mono_slot_count(dlens.table, zp)
-    if tape is not None and mode == _abi.VJP_ADJOINT:
-        # the forward wrote the tape (ort_options.tape): reverse sweep only, the final
-        # state read from the forward's outputs
-        params.tape = tape.data_ptr()
-        params.primal = _native.ort_rays(*(t.data_ptr() for t in primal))
-    if rms is not None:
-        if mode != _abi.VJP_ADJOINT:
-            raise ValueError("vjp: the rms cotangent fold is the adjoint mode's")
-        params.rms_stats, params.rms_grad = rms[0].data_ptr(), rms[1].data_ptr()
-    # both modes take a workspace (ABI v15: the unrolled mode's block partials)
-    size = lib.ort_vjp_workspace_size(C.byref(dlens.c), C.byref(batch), C.byref(params))
-    _native.check(int(size) if size < 0 else 0, "ort_vjp_workspace_size")
-    ws = _workspace(grad.device, size)
-    params.workspace = ws.data_ptr()
-    params.workspace_size = ws.numel()
-    cot_c = _native.ort_rays(*(0 if c is None else c.data_ptr() for c in cot))
+    # a tape the forward wrote (ort_options.tape): the adjoint is the reverse sweep only,
+    # its final state read from the forward's outputs
+    taped = tape is not None and mode == _abi.VJP_ADJOINT
+    params = _calls.vjp_params(dlens.table, n_param, mode, tables[:3], need, overwrite,
+                               tape=tape if taped else None, primal=primal, rms=rms)
+    _calls.attach_vjp_workspace(lib, dlens.c, batch, params, "pupil_vjp", grad.device)
+    cot_c = _calls.rays_struct(cot)
     timer = VJP_EVENTS
     if timer is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record(torch.cuda.current_stream())
-    rc = lib.ort_trace_pupil_vjp(C.byref(dlens.c), _ptr(px), _ptr(py), C.byref(batch),
-                                 C.byref(opt), C.byref(params), C.byref(cot_c), _ptr(grad),
+    rc = lib.ort_trace_pupil_vjp(C.byref(dlens.c), addr(px), addr(py), C.byref(batch),
+                                 C.byref(opt), C.byref(params), C.byref(cot_c), addr(grad),
                                  _stream_handle())
     _native.check(rc, "ort_trace_pupil_vjp")
     if timer is not None:

@@ -85,17 +85,17 @@ def _agree_newton_schedule(dl, keys, segs, px, py, out, n, n_loc, group):
         # the pair's global stopping index, which no rank's own check can contradict)
         import ctypes as C
 
-        from . import _abi, _native
-        from .raytrace import _ptr, _stream_handle, upload_segments
+        from . import _abi, _calls, _native
+        from ._calls import addr
+        from .raytrace import _stream_handle, upload_segments
 
         lib = _native.load()
         seg_dev = upload_segments(segs, dl.device)
-        batch = _native.ort_batch(n, n_loc, n_loc, len(segs), 0, seg_dev.data_ptr())
-        batch.apod = None if dl.apod is None else dl.apod.data_ptr()
+        batch = _calls.pupil_batch(n, n_loc, n_loc, seg_dev, False, dl.apod)
         sched_dev = torch.as_tensor(agreed.reshape(-1), device=dl.device)
-        opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, sched_dev.data_ptr())
+        opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, addr(sched_dev))
         out_c = out.c_struct()
-        rc = lib.ort_trace_pupil(C.byref(dl.c), _ptr(px), _ptr(py), C.byref(out_c),
+        rc = lib.ort_trace_pupil(C.byref(dl.c), addr(px), addr(py), C.byref(out_c),
                                  C.byref(batch), C.byref(opt), None, None, None,
                                  _stream_handle())
         _native.check(rc, "ort_trace_pupil")

@@ -18,16 +18,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi, _native
+from . import _abi, _calls, _native
+from ._calls import addr, rays_struct
 
-
-def _p(a):
-    """Host address of a numpy array or CPU tensor (None: NULL)."""
-    if a is None:
-        return None
-    if torch.is_tensor(a):
-        return a.data_ptr()
-    return a.ctypes.data
+_rays_c = rays_struct  # (the name tests/test_polarization_cpu.py builds its structs with)
 
 
 class HostLens:
@@ -58,9 +52,9 @@ class HostLens:
             mask |= 1 << int(g)
         self.geometry_mask = mask
         self.c = _native.ort_lens(
-            _p(surfaces), _p(cs_ops), _p(coef), _p(zern), _p(n_tab), _p(alpha_tab), _p(optics),
+            addr(surfaces), addr(cs_ops), addr(coef), addr(zern), addr(n_tab), addr(alpha_tab), addr(optics),
             table.n_surfaces, len(table.wavelengths), table.n_tab.shape[1], table.final_mat,
-            mask, table.interaction_mask, table.final_thickness, _p(mats), _p(lambdas),
+            mask, table.interaction_mask, table.final_thickness, addr(mats), addr(lambdas),
             table.frame_flags)
         self._keep = keep
         # the same nine tables as torch CPU tensors sharing these arrays' memory (the lens as
@@ -92,10 +86,6 @@ class HostLens:
         return t
 
 
-def _rays_c(ts):
-    return _native.ort_rays(*(0 if t is None else t.data_ptr() for t in ts))
-
-
 def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec):
     """ort_host_trace_sequential of resident CPU rays (8 contiguous float64 tensors):
     returns the 8 output tensors and the Newton update counts [S] (int32 tensor) the
@@ -105,27 +95,19 @@ def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec):
     lib = _native.load_host()
     n = rays_in[0].numel()
     outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
-    batch = _native.ort_batch(n, max(n, 1), max(n, 1), 0, 0, None)
+    batch = _calls.resident_batch(n)
     w_keep = None
     if per_ray_w:
-        w_keep = w.detach().to(dtype=torch.float64).reshape(-1)
-        w_keep = w_keep.expand(n).contiguous() if w_keep.numel() == 1 else w_keep.contiguous()
-        if w_keep.numel() != n:
-            raise ValueError("rays.w must hold one wavelength per ray")
-        mt = hl.table.mat_table
-        if mt is not None and np.any(mt["kind"] == _abi.MAT_ABBE):
-            # abbe.py:47-48 raises before any n is used
-            if bool(((w_keep < 0.380) | (w_keep > 0.750)).any()):
-                raise ValueError("Wavelength out of range for this model.")
-        batch.w = w_keep.data_ptr()
+        w_keep = _calls.per_ray_wavelengths(hl.table, w, n, hl.device, validate=True)
+        batch.w = addr(w_keep)
     S = hl.table.n_surfaces
     updates = torch.zeros(S, dtype=torch.int32)
     status = np.zeros(1, dtype=np.int32)
     opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
-    rin_c, out_c = _rays_c(rays_in), _rays_c(outs)
+    rin_c, out_c = rays_struct(rays_in), rays_struct(outs)
     rc = lib.ort_host_trace_sequential(C.byref(hl.c), C.byref(rin_c), C.byref(out_c),
-                                       C.byref(batch), C.byref(opt), _p(rec),
-                                       _p(updates), _p(status))
+                                       C.byref(batch), C.byref(opt), addr(rec),
+                                       addr(updates), addr(status))
     _native.check(rc, "ort_host_trace_sequential")
     _raise_status_value(int(status[0]))
     return outs, updates
@@ -137,25 +119,19 @@ def trace_sequential_vjp(hl: HostLens, rays_in, w, per_ray_w, start_surface, sch
     tabs: (zern_param, surf_tangent, final_tangent) CPU tensors or None."""
     lib = _native.load_host()
     n = rays_in[0].numel()
-    batch = _native.ort_batch(n, max(n, 1), max(n, 1), 0, 0, None)
+    batch = _calls.resident_batch(n)
     w_keep = None
     if per_ray_w:
-        w_keep = w.to(dtype=torch.float64).reshape(-1)
-        w_keep = w_keep.expand(n).contiguous() if w_keep.numel() == 1 else w_keep.contiguous()
-        batch.w = w_keep.data_ptr()
+        w_keep = _calls.per_ray_wavelengths(hl.table, w, n, hl.device, validate=False)
+        batch.w = addr(w_keep)
     sched_c = sched if sched is not None and sched.numel() else None
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), _p(sched_c))
-    zp, st, ft = tabs
-    params = _native.ort_vjp_params(int(n_param), int(mode), _p(zp), _p(st), _p(ft),
-                                    0 if zp is None else int(zp.numel()), 0, None, 0, _p(need))
-    from .ops import mono_slot_count
-
-    params.n_mono = mono_slot_count(hl.table, None if zp is None else zp.numpy())
+    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), addr(sched_c))
+    params = _calls.vjp_params(hl.table, n_param, mode, tabs, need, grad_init=False)
     rc = lib.ort_host_trace_sequential_vjp(
-        C.byref(hl.c), C.byref(_rays_c(rays_in)), C.byref(batch), C.byref(opt),
-        C.byref(params), C.byref(_rays_c(cot)), _p(rec_cot),
-        _p(rec if rec_cot is not None else None), _p(grad),
-        C.byref(_rays_c(gin if gin is not None else [None] * 8)))
+        C.byref(hl.c), C.byref(rays_struct(rays_in)), C.byref(batch), C.byref(opt),
+        C.byref(params), C.byref(rays_struct(cot)), addr(rec_cot),
+        addr(rec if rec_cot is not None else None), addr(grad),
+        C.byref(rays_struct(gin if gin is not None else [None] * 8)))
     _native.check(rc, "ort_host_trace_sequential_vjp")
     del w_keep
 
@@ -167,21 +143,18 @@ def trace_pupil(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, apod=None)
     from .raytrace import _raise_status_value
 
     lib = _native.load_host()
-    n_seg = seg.numel() // _abi.SEGMENT.itemsize
     outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
     # one Newton group: the whole call, as RealRayTracer.trace traces every field of a
     # wavelength in one SurfaceGroup.trace (real_ray_tracer.py:37-97)
-    batch = _native.ort_batch(n, max(seg_len, 1), max(n, 1), n_seg, int(pupil_per_ray),
-                              seg.data_ptr())
-    batch.apod = None if apod is None else apod.data_ptr()
+    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
     S = hl.table.n_surfaces
     n_groups = 1 if n else 0
     updates = torch.zeros(max(1, n_groups) * S, dtype=torch.int32)
     status = np.zeros(1, dtype=np.int32)
     opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
-    out_c = _rays_c(outs)
-    rc = lib.ort_host_trace_pupil(C.byref(hl.c), _p(px), _p(py), C.byref(out_c), C.byref(batch),
-                                  C.byref(opt), _p(updates), _p(status))
+    out_c = rays_struct(outs)
+    rc = lib.ort_host_trace_pupil(C.byref(hl.c), addr(px), addr(py), C.byref(out_c),
+                                  C.byref(batch), C.byref(opt), addr(updates), addr(status))
     _native.check(rc, "ort_host_trace_pupil")
     _raise_status_value(int(status[0]))
     return outs, updates[:n_groups * S]
@@ -192,23 +165,14 @@ def trace_pupil_vjp(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, sched,
     """ort_host_trace_pupil_vjp: grad = J^T cot of the pupil trace (grad overwritten).
     rms: (stats[5], g[1]) of an rms spot size of the outputs, folded into the x, y
     cotangents (ort_vjp_params.rms_stats / rms_grad; the adjoint mode)."""
-    from .ops import mono_slot_count
-
     lib = _native.load_host()
-    n_seg = seg.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n, max(seg_len, 1), max(n, 1), n_seg, int(pupil_per_ray),
-                              seg.data_ptr())
-    batch.apod = None if apod is None else apod.data_ptr()
+    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
     sched_c = sched if sched is not None and sched.numel() else None
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, _p(sched_c))
-    zp, st, ft = tabs
-    params = _native.ort_vjp_params(int(n_param), int(mode), _p(zp), _p(st), _p(ft),
-                                    0 if zp is None else int(zp.numel()), 1, None, 0, _p(need))
-    params.n_mono = mono_slot_count(hl.table, None if zp is None else zp.numpy())
-    if rms is not None:
-        params.rms_stats, params.rms_grad = _p(rms[0]), _p(rms[1])
-    rc = lib.ort_host_trace_pupil_vjp(C.byref(hl.c), _p(px), _p(py), C.byref(batch), C.byref(opt),
-                                      C.byref(params), C.byref(_rays_c(cot)), _p(grad))
+    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, addr(sched_c))
+    params = _calls.vjp_params(hl.table, n_param, mode, tabs, need, grad_init=True, rms=rms)
+    rc = lib.ort_host_trace_pupil_vjp(C.byref(hl.c), addr(px), addr(py), C.byref(batch),
+                                      C.byref(opt), C.byref(params), C.byref(rays_struct(cot)),
+                                      addr(grad))
     _native.check(rc, "ort_host_trace_pupil_vjp")
 
 
@@ -217,7 +181,7 @@ def rms_spot(x, y):
     lib = _native.load_host()
     stats = torch.empty(5, dtype=torch.float64)
     rms = torch.empty((), dtype=torch.float64)
-    rc = lib.ort_host_rms_spot(_p(x), _p(y), x.numel(), _p(stats), _p(rms))
+    rc = lib.ort_host_rms_spot(addr(x), addr(y), x.numel(), addr(stats), addr(rms))
     _native.check(rc, "ort_host_rms_spot")
     return rms, stats
 
@@ -225,7 +189,7 @@ def rms_spot(x, y):
 def rms_spot_vjp(x, y, stats, g):
     lib = _native.load_host()
     gx, gy = torch.empty_like(x), torch.empty_like(y)
-    rc = lib.ort_host_rms_spot_vjp(_p(x), _p(y), x.numel(), _p(stats), _p(g), _p(gx), _p(gy))
+    rc = lib.ort_host_rms_spot_vjp(addr(x), addr(y), x.numel(), addr(stats), addr(g), addr(gx), addr(gy))
     _native.check(rc, "ort_host_rms_spot_vjp")
     return gx, gy
 
@@ -235,9 +199,9 @@ def huygens_psf(image, pupil, wavelength_mm, rp):
     (image = x, y, z; pupil = x, y, z, amp, opd in mm)."""
     lib = _native.load_host()
     psf = torch.empty(image[0].numel(), dtype=torch.float64)
-    rc = lib.ort_host_huygens_psf(*(_p(t) for t in image), image[0].numel(),
-                                  *(_p(t) for t in pupil), pupil[0].numel(),
-                                  float(wavelength_mm), float(rp), _p(psf))
+    rc = lib.ort_host_huygens_psf(*(addr(t) for t in image), image[0].numel(),
+                                  *(addr(t) for t in pupil), pupil[0].numel(),
+                                  float(wavelength_mm), float(rp), addr(psf))
     _native.check(rc, "ort_host_huygens_psf")
     return psf
 
@@ -248,8 +212,8 @@ def irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=0.0):
     lib = _native.load_host()
     nx, ny = x_edges.numel() - 1, y_edges.numel() - 1
     out = torch.empty(max(nx * ny, 0), dtype=torch.float64)
-    rc = lib.ort_host_irradiance_bin(_p(x), _p(y), _p(power), x.numel(), _p(x_edges), nx,
-                                     _p(y_edges), ny, int(mode), float(pixel_area), _p(out))
+    rc = lib.ort_host_irradiance_bin(addr(x), addr(y), addr(power), x.numel(), addr(x_edges), nx,
+                                     addr(y_edges), ny, int(mode), float(pixel_area), addr(out))
     _native.check(rc, "ort_host_irradiance_bin")
     return out
 
@@ -259,8 +223,8 @@ def irradiance_bin_vjp(x, y, power, x_edges, y_edges, grad, pixel_area=0.0):
     lib = _native.load_host()
     nx, ny = x_edges.numel() - 1, y_edges.numel() - 1
     gx, gy, gp = (torch.empty(x.numel(), dtype=torch.float64) for _ in range(3))
-    rc = lib.ort_host_irradiance_bin_vjp(_p(x), _p(y), _p(power), x.numel(), _p(x_edges), nx,
-                                         _p(y_edges), ny, float(pixel_area), _p(grad), _p(gx),
-                                         _p(gy), _p(gp))
+    rc = lib.ort_host_irradiance_bin_vjp(addr(x), addr(y), addr(power), x.numel(), addr(x_edges), nx,
+                                         addr(y_edges), ny, float(pixel_area), addr(grad), addr(gx),
+                                         addr(gy), addr(gp))
     _native.check(rc, "ort_host_irradiance_bin_vjp")
     return gx, gy, gp

@@ -55,14 +55,14 @@ ort::irradiance_bin_vjp (a gather); the histogram mode refuses inputs that requi
 from __future__ import annotations
 
 import ctypes as C
-import weakref
-
 import os
+import weakref
 
 import numpy as np
 import torch
 
-from . import _abi, _native
+from . import _abi, _calls, _native
+from ._calls import addr
 
 SPEC_KINDS = ("zernike", "radius", "conic", "thickness", "vertex")
 
@@ -247,22 +247,6 @@ def _check_differentiable(table, adjoint=False):
                                   "forward-mode VJP carries parameter tangents only)")
 
 
-_WORKSPACE: dict = {}
-
-
-def _workspace(device, nbytes):
-    ws = _WORKSPACE.get(device)
-    if ws is None or ws.numel() < nbytes:
-        _WORKSPACE.pop(device, None)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _WORKSPACE[device] = ws
-    return ws
-
-
-def _ray_struct(ts):
-    return _native.ort_rays(*(0 if t is None else t.data_ptr() for t in ts))
-
-
 # --------------------------------------------------------------------------------------
 # the lens as the ops take it (the op is self-describing)
 # --------------------------------------------------------------------------------------
@@ -352,8 +336,27 @@ def _resolve(lens, meta, final_thickness, key):
     return hit
 
 
-def _opt(t):
-    return None if t is None else t
+def _schedule_tensor(dl):
+    """The Newton schedule the last trace of `dl` settled on, as a fresh int32 tensor on the
+    lens's device that the caller owns (empty: no Newton surfaces)."""
+    if dl.last_schedule_dev is not None:  # device-verified: the settled device schedule
+        return (dl.last_schedule_dev if dl.last_schedule_private  # a per-call copy
+                else dl.last_schedule_dev.clone())
+    if dl.last_schedule is None:
+        return torch.empty(0, dtype=torch.int32, device=dl.device)
+    # host-verified: a device clone of the resident copy its last launch read (no upload)
+    return dl.resident("sched", dl.last_schedule.reshape(-1)).clone()
+
+
+def _split_param_grads(g, shapes):
+    """The flat parameter gradient cut back into the parameters' (shape, dtype, device)."""
+    res = []
+    off = 0
+    for shape, dtype, pdev in shapes:
+        k = int(np.prod(shape)) if len(shape) else 1
+        res.append(g[off:off + k].reshape(shape).to(device=pdev, dtype=dtype))
+        off += k
+    return res
 
 
 # --------------------------------------------------------------------------------------
@@ -385,15 +388,7 @@ def trace_sequential(lens: list[torch.Tensor], lens_meta: list[int], final_thick
     rec = torch.empty(n_rec * 8 * n, dtype=torch.float64, device=dev)
     trace_rays(dl, rin, rout, rec=rec if n_rec else None, start_surface=int(start_surface),
                per_ray_w=bool(per_ray_w))
-    sched = dl.last_schedule
-    if dl.last_schedule_dev is not None:  # device-verified: the settled device schedule
-        sched_t = (dl.last_schedule_dev if dl.last_schedule_private  # a per-call copy
-                   else dl.last_schedule_dev.clone())
-    elif sched is None:
-        sched_t = torch.empty(0, dtype=torch.int32, device=dev)
-    else:
-        sched_t = torch.from_numpy(np.ascontiguousarray(sched.reshape(-1), dtype=np.int32)).to(dev)
-    return (*(getattr(rout, a) for a in _abi.RAY_FIELDS), rec, sched_t)
+    return (*(getattr(rout, a) for a in _abi.RAY_FIELDS), rec, _schedule_tensor(dl))
 
 
 @trace_sequential.register_kernel("cpu")
@@ -498,14 +493,7 @@ def _seq_backward(ctx, *grads):
     ray_grads = none_rays
     if want_rays:
         ray_grads = [gi.reshape(s).to(d) for gi, (s, d) in zip(gin, ctx.ray_meta, strict=True)]
-    param_grads = none_params
-    if want_params:
-        param_grads = []
-        off = 0
-        for shape, dtype, pdev in ctx.shapes:
-            k = int(np.prod(shape)) if len(shape) else 1
-            param_grads.append(g[off:off + k].reshape(shape).to(device=pdev, dtype=dtype))
-            off += k
+    param_grads = _split_param_grads(g, ctx.shapes) if want_params else none_params
     return (*nothing, ray_grads, None, param_grads, none_spec, None, None)
 
 
@@ -537,13 +525,8 @@ def trace_sequential_vjp(lens: list[torch.Tensor], lens_meta: list[int], final_t
                         start_surface, per_ray_w, want_rays)
 
 
-@trace_sequential_vjp.register_kernel("cpu")
-def _trace_sequential_vjp_cpu(lens, lens_meta, final_thickness, lens_key, rays_in, w, sched, rec,
-                              cot, rec_cot, tables, n_param, mode, start_surface, per_ray_w,
-                              want_rays):
-    dl = _resolve(lens, lens_meta, final_thickness, lens_key)
-    return _seq_vjp_run(dl, rays_in, w, sched, rec, cot, rec_cot, tables, n_param, mode,
-                        start_surface, per_ray_w, want_rays)
+# the CPU dispatch key: the same function (_seq_vjp hands a HostLens to the host library)
+trace_sequential_vjp.register_kernel("cpu")(trace_sequential_vjp._init_fn)
 
 
 @trace_sequential_vjp.register_fake
@@ -576,50 +559,36 @@ def _seq_vjp(dl, rays_in, w, per_ray_w, start_surface, sched, zp, st, ft, n_para
     """One ort_trace_sequential_vjp call (grad += J^T cot, gin = input-ray cotangents); on
     a HostLens the host library's ort_host_trace_sequential_vjp."""
     from . import host
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     if need is None and mode == _abi.VJP_ADJOINT and zp is not None:
         need = slot_need(dl.table, zp, st, ft)
+    tabs = [None if a is None else dl.resident(("seq_tangent", i), a)
+            for i, a in enumerate((zp, st, ft))]
+    need_t = None if need is None else dl.resident("seq_need", need)
     if isinstance(dl, host.HostLens):
-        tabs = [None if a is None else dl.resident(("seq_tangent", i), a)
-                for i, a in enumerate((zp, st, ft))]
-        need_t = None if need is None else dl.resident("seq_need", need)
         host.trace_sequential_vjp(dl, rays_in, w, per_ray_w, start_surface, sched, tabs, need_t,
                                   n_param, mode, cot, rec_cot, rec, grad, gin)
         return
 
     lib = _native.load()
     n = rays_in[0].numel()
-    batch = _native.ort_batch(n, max(n, 1), max(n, 1), 0, 0, None)
+    batch = _calls.resident_batch(n)
     w_keep = None
     if per_ray_w:
-        w_keep = w.to(device=dl.device, dtype=torch.float64).reshape(-1)
-        w_keep = w_keep.expand(n).contiguous() if w_keep.numel() == 1 else w_keep.contiguous()
-        batch.w = w_keep.data_ptr()
+        w_keep = _calls.per_ray_wavelengths(dl.table, w, n, dl.device, validate=False)
+        batch.w = addr(w_keep)
     sched_dev = sched if sched is not None and sched.numel() else None
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface),
-                              None if sched_dev is None else sched_dev.data_ptr())
-    tabs = [None if a is None else dl.resident(("seq_tangent", i), a)
-            for i, a in enumerate((zp, st, ft))]
-    need_t = None if need is None else dl.resident("seq_need", need)
-    params = _native.ort_vjp_params(int(n_param), int(mode), _ptr(tabs[0]).value,
-                                    _ptr(tabs[1]).value, _ptr(tabs[2]).value,
-                                    0 if tabs[0] is None else int(tabs[0].numel()), 0, None, 0,
-                                    _ptr(need_t).value)
-    params.n_mono = mono_slot_count(dl.table, zp) if mode == _abi.VJP_ADJOINT else 0
-    # both modes take a workspace (ABI v15: the unrolled mode's block partials)
-    size = lib.ort_vjp_workspace_size(C.byref(dl.c), C.byref(batch), C.byref(params))
-    _native.check(int(size) if size < 0 else 0, "ort_vjp_workspace_size")
-    ws = _workspace(dl.device, size)
-    params.workspace = ws.data_ptr()
-    params.workspace_size = ws.numel()
-    rin_c = _ray_struct(rays_in)
-    cot_c = _ray_struct(cot)
-    gin_c = _ray_struct(gin if gin is not None else [None] * 8)
+    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), addr(sched_dev))
+    params = _calls.vjp_params(dl.table, n_param, mode, tabs, need_t, grad_init=False)
+    _calls.attach_vjp_workspace(lib, dl.c, batch, params, "seq_vjp", dl.device)
+    rin_c = _calls.rays_struct(rays_in)
+    cot_c = _calls.rays_struct(cot)
+    gin_c = _calls.rays_struct(gin if gin is not None else [None] * 8)
     rc = lib.ort_trace_sequential_vjp(C.byref(dl.c), C.byref(rin_c), C.byref(batch),
                                       C.byref(opt), C.byref(params), C.byref(cot_c),
-                                      _ptr(rec_cot), _ptr(rec if rec_cot is not None else None),
-                                      _ptr(grad), C.byref(gin_c), _stream_handle())
+                                      addr(rec_cot), addr(rec if rec_cot is not None else None),
+                                      addr(grad), C.byref(gin_c), _stream_handle())
     _native.check(rc, "ort_trace_sequential_vjp")
     del w_keep, tabs  # ordered on the stream before any reuse of their memory
 
@@ -691,15 +660,8 @@ def trace_pupil(lens: list[torch.Tensor], lens_meta: list[int], final_thickness:
     _trace(dl, seg, px, py, out, n, seg_len, n, keys=_plan_keys(plan_key),
            pupil_per_ray=bool(ppr), newton_mode=NEWTON_MODES[mode],
            tape=tape if want_tape else None, rms=(rms, rms_stats) if want_rms else None)
-    sched = dl.last_schedule
-    if dl.last_schedule_dev is not None:  # device-verified: the settled device schedule
-        sched_t = (dl.last_schedule_dev if dl.last_schedule_private  # a per-call copy
-                   else dl.last_schedule_dev.clone())
-    elif sched is None:
-        sched_t = torch.empty(0, dtype=torch.int32, device=dl.device)
-    else:
-        sched_t = dl.resident("sched", sched.reshape(-1)).clone()
-    return (*(getattr(out, a) for a in _abi.RAY_FIELDS), sched_t, tape, rms, rms_stats)
+    return (*(getattr(out, a) for a in _abi.RAY_FIELDS), _schedule_tensor(dl), tape, rms,
+            rms_stats)
 
 
 @trace_pupil.register_kernel("cpu")
@@ -786,13 +748,7 @@ def _pupil_backward(ctx, *grads):
                                       seg, apod, px, py, sched, tape, primal, cot, tabs,
                                       n_param, int(mode), ctx.plan_meta,
                                       rms_stats if g_rms is not None else None, g_rms)
-    res = []
-    off = 0
-    for shape, dtype, pdev in ctx.shapes:
-        k = int(np.prod(shape)) if len(shape) else 1
-        res.append(g[off:off + k].reshape(shape).to(device=pdev, dtype=dtype))
-        off += k
-    return (*nothing, res, none_spec, None, None)
+    return (*nothing, _split_param_grads(g, ctx.shapes), none_spec, None, None)
 
 
 trace_pupil.register_autograd(_pupil_backward, setup_context=_pupil_setup)
@@ -860,23 +816,11 @@ def _(lens, lens_meta, final_thickness, lens_key, seg, apod, px, py, sched, tape
 # --------------------------------------------------------------------------------------
 # ort::rms_spot -- RayOperand.rms_spot_size's reduction (optimization/operand/ray.py:300-340)
 # --------------------------------------------------------------------------------------
-_RMS_WS: dict = {}
-
-
 def _rms_workspace(device, n):
     lib = _native.load()
     size = int(lib.ort_rms_spot_workspace_size(int(n)))
     _native.check(size if size < 0 else 0, "ort_rms_spot_workspace_size")
-    return _workspace_named(_RMS_WS, device, size), size
-
-
-def _workspace_named(cache, device, nbytes):
-    ws = cache.get(device)
-    if ws is None or ws.numel() < nbytes:
-        cache.pop(device, None)
-        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
-        cache[device] = ws
-    return ws
+    return _calls.workspace("rms", device, size), size
 
 
 @torch.library.custom_op("ort::rms_spot", mutates_args=(), device_types="cuda")
@@ -884,7 +828,7 @@ def rms_spot(x: torch.Tensor, y: torch.Tensor) -> tuple[torch.Tensor, torch.Tens
     """(rms, stats[5] = n, mean x, mean y, rms, max radius): sqrt(mean((x - mean x)^2 +
     (y - mean y)^2)) as the reference's operand forms it, two deterministic passes on the
     device (ort_rms_spot), no host synchronisation."""
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     lib = _native.load()
     _check_rms_inputs(x, y)
@@ -894,7 +838,7 @@ def rms_spot(x: torch.Tensor, y: torch.Tensor) -> tuple[torch.Tensor, torch.Tens
     ws, size = _rms_workspace(x.device, n)
     stats = torch.empty(5, dtype=torch.float64, device=x.device)
     rms = torch.empty((), dtype=torch.float64, device=x.device)
-    rc = lib.ort_rms_spot(_ptr(x), _ptr(y), n, _ptr(ws), size, _ptr(stats), _ptr(rms),
+    rc = lib.ort_rms_spot(addr(x), addr(y), n, addr(ws), size, addr(stats), addr(rms),
                           _stream_handle())
     _native.check(rc, "ort_rms_spot")
     return rms, stats
@@ -951,15 +895,15 @@ rms_spot.register_autograd(_rms_backward, setup_context=_rms_setup)
 def rms_spot_vjp(x: torch.Tensor, y: torch.Tensor, stats: torch.Tensor,
                  g: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """ort_rms_spot_vjp: g (x - mean x, y - mean y) / (n rms) (one kernel)."""
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     xf = x.detach().reshape(-1).contiguous()
     yf = y.detach().reshape(-1).contiguous()
     gg = g.detach().to(torch.float64).contiguous()
     gx = torch.empty_like(xf)
     gy = torch.empty_like(yf)
-    rc = _native.load().ort_rms_spot_vjp(_ptr(xf), _ptr(yf), xf.numel(), _ptr(stats), _ptr(gg),
-                                         _ptr(gx), _ptr(gy), _stream_handle())
+    rc = _native.load().ort_rms_spot_vjp(addr(xf), addr(yf), xf.numel(), addr(stats), addr(gg),
+                                         addr(gx), addr(gy), _stream_handle())
     _native.check(rc, "ort_rms_spot_vjp")
     return gx, gy
 
@@ -1012,7 +956,7 @@ def huygens_psf(image_x: torch.Tensor, image_y: torch.Tensor, image_z: torch.Ten
     (image tile, pupil chunk) and a fixed-order sum of the chunk partials on the current
     stream, no host synchronisation. Not differentiable (yet): a requires_grad input
     raises NotImplementedError."""
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     lib = _native.load()
     image, pupil = (image_x, image_y, image_z), (pupil_x, pupil_y, pupil_z, amp, opd_mm)
@@ -1023,8 +967,8 @@ def huygens_psf(image_x: torch.Tensor, image_y: torch.Tensor, image_z: torch.Ten
     _native.check(size if size < 0 else 0, "ort_huygens_workspace_size")
     ws = torch.empty(max(size, 8), dtype=torch.uint8, device=image_x.device)
     psf = torch.empty(n_i, dtype=torch.float64, device=image_x.device)
-    rc = lib.ort_huygens_psf(*(_ptr(t) for t in fi), n_i, *(_ptr(t) for t in fp), n_p,
-                             float(wavelength_mm), float(rp), _ptr(psf), _ptr(ws), size,
+    rc = lib.ort_huygens_psf(*(addr(t) for t in fi), n_i, *(addr(t) for t in fp), n_p,
+                             float(wavelength_mm), float(rp), addr(psf), addr(ws), size,
                              _stream_handle())
     _native.check(rc, "ort_huygens_psf")
     return psf.reshape(image_x.shape)
@@ -1126,7 +1070,7 @@ def irradiance_bin(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
     pixel's, from the edges). BIN_HISTOGRAM returns [nx, ny] (X is the row index, as
     numpy.histogram2d), BIN_BILINEAR [ny, nx] (Y is the row index, as the reference's
     index_put): the reference's two paths differ in orientation and so do these."""
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     lib = _native.load()
     nx, ny = _check_irradiance_inputs(x, y, power, x_edges, y_edges, mode)
@@ -1136,9 +1080,9 @@ def irradiance_bin(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
     _native.check(size if size < 0 else 0, "ort_irradiance_workspace_size")
     ws = torch.empty(size, dtype=torch.uint8, device=x.device)
     out = torch.empty(nx * ny, dtype=torch.float64, device=x.device)
-    rc = lib.ort_irradiance_bin(_ptr(fx), _ptr(fy), _ptr(fp), fx.numel(), _ptr(ex), nx,
-                                _ptr(ey), ny, int(mode), float(pixel_area or 0.0), _ptr(out),
-                                _ptr(ws), size, _stream_handle())
+    rc = lib.ort_irradiance_bin(addr(fx), addr(fy), addr(fp), fx.numel(), addr(ex), nx,
+                                addr(ey), ny, int(mode), float(pixel_area or 0.0), addr(out),
+                                addr(ws), size, _stream_handle())
     _native.check(rc, "ort_irradiance_bin")
     return out.reshape(_irr_shape(nx, ny, mode))
 
@@ -1174,7 +1118,7 @@ def irradiance_bin_vjp(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
                        ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """ort_irradiance_bin_vjp: the gradients of a scalar with respect to x, y and power, given
     its gradient `grad` [ny, nx] with respect to the BIN_BILINEAR map."""
-    from .raytrace import _ptr, _stream_handle
+    from .raytrace import _stream_handle
 
     lib = _native.load()
     op = "ort::irradiance_bin_vjp"
@@ -1184,9 +1128,9 @@ def irradiance_bin_vjp(x: torch.Tensor, y: torch.Tensor, power: torch.Tensor,
     fx, fy, fp, ex, ey, fg = _flat((x, y, power, x_edges, y_edges, grad))
     gx, gy, gp = (torch.empty(fx.numel(), dtype=torch.float64, device=x.device)
                   for _ in range(3))
-    rc = lib.ort_irradiance_bin_vjp(_ptr(fx), _ptr(fy), _ptr(fp), fx.numel(), _ptr(ex), nx,
-                                    _ptr(ey), ny, float(pixel_area or 0.0), _ptr(fg),
-                                    _ptr(gx), _ptr(gy), _ptr(gp), _stream_handle())
+    rc = lib.ort_irradiance_bin_vjp(addr(fx), addr(fy), addr(fp), fx.numel(), addr(ex), nx,
+                                    addr(ey), ny, float(pixel_area or 0.0), addr(fg),
+                                    addr(gx), addr(gy), addr(gp), _stream_handle())
     _native.check(rc, op)
     return gx.reshape(x.shape), gy.reshape(y.shape), gp.reshape(power.shape)
 

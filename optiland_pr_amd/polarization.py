@@ -19,7 +19,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, _native
+from . import _abi, _calls, _native
+from ._calls import addr
 from .raytrace import RealRays
 
 try:
@@ -258,18 +259,14 @@ def _host_launch(hl, seg, px, py, outs, n, seg_len, pupil_per_ray, rec, pol, apo
     from .raytrace import _raise_status_value
 
     lib = _native.load_host()
-    n_seg = seg.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n, max(seg_len, 1), max(n, 1), n_seg, int(pupil_per_ray),
-                              seg.data_ptr())
-    batch.apod = None if apod is None else apod.data_ptr()
+    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
     status = np.zeros(1, dtype=np.int32)
     updates = np.zeros(max(1, hl.table.n_surfaces), dtype=np.int32)
     opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
-    out_c = _native.ort_rays(*(t.data_ptr() for t in outs))
+    out_c = _calls.rays_struct(outs)
     rc = lib.ort_host_trace_pupil_polarized(
-        C.byref(hl.c), px.data_ptr(), py.data_ptr(), C.byref(out_c), C.byref(batch),
-        C.byref(opt), None if rec is None else rec.data_ptr(), updates.ctypes.data,
-        status.ctypes.data, C.byref(pol))
+        C.byref(hl.c), addr(px), addr(py), C.byref(out_c), C.byref(batch), C.byref(opt),
+        addr(rec), addr(updates), addr(status), C.byref(pol))
     _native.check(rc, "ort_host_trace_pupil_polarized")
     _raise_status_value(int(status[0]))
 
@@ -304,8 +301,7 @@ def trace_pupil_polarized(lens, segs, px, py, n, seg_len, mode, state, pupil_per
         coat = _coatings_of(lens)
     if isinstance(apod, str):
         apod = _apod_of(lens)
-    pol = polarization_struct(mode, state, coat.data_ptr(),
-                              None if planes is None else planes.data_ptr(), field)
+    pol = polarization_struct(mode, state, addr(coat), addr(planes), field)
     if dev.type == "cpu":
         seg = segs if torch.is_tensor(segs) else _bytes_tensor(
             np.asarray(segs, dtype=_abi.SEGMENT))
@@ -314,18 +310,14 @@ def trace_pupil_polarized(lens, segs, px, py, n, seg_len, mode, state, pupil_per
     lib = _native.load()
     seg_dev = (segs if torch.is_tensor(segs) else
                lens.resident("segments", np.asarray(segs, dtype=_abi.SEGMENT)))
-    n_seg = seg_dev.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n, seg_len, max(n, 1), n_seg, int(pupil_per_ray),
-                              seg_dev.data_ptr())
-    batch.apod = raytrace._addr(apod)
-    out_c = _native.ort_rays(*(t.data_ptr() for t in outs))
+    batch = _calls.pupil_batch(n, seg_len, n, seg_dev, pupil_per_ray, apod)
+    out_c = _calls.rays_struct(outs)
     stream = raytrace._stream_handle()
 
     def launch(opt, stats, status):
         rc = lib.ort_trace_pupil_polarized(
-            C.byref(lens.c), raytrace._ptr(px), raytrace._ptr(py), C.byref(out_c),
-            C.byref(batch), C.byref(opt), raytrace._ptr(rec), raytrace._ptr(stats),
-            raytrace._ptr(status), C.byref(pol), stream)
+            C.byref(lens.c), addr(px), addr(py), C.byref(out_c), C.byref(batch),
+            C.byref(opt), addr(rec), addr(stats), addr(status), C.byref(pol), stream)
         _native.check(rc, "ort_trace_pupil_polarized")
 
     raytrace._run(lens, launch, n, max(n, 1), list(keys), newton_mode)
@@ -343,11 +335,9 @@ def trace_sequential_polarized(lens, rays_in, mode, state, rec=None, want_p=True
     outs = [torch.empty(n, dtype=torch.float64, device=dev) for _ in range(8)]
     planes = torch.empty(18 * n, dtype=torch.float64, device=dev) if want_p else None
     coat = _coatings_of(lens)
-    pol = polarization_struct(mode, state, coat.data_ptr(),
-                              None if planes is None else planes.data_ptr())
-    batch = _native.ort_batch(n, max(n, 1), max(n, 1), 0, 0, None)
-    in_c = _native.ort_rays(*(t.data_ptr() for t in rays_in))
-    out_c = _native.ort_rays(*(t.data_ptr() for t in outs))
+    pol = polarization_struct(mode, state, addr(coat), addr(planes))
+    batch = _calls.resident_batch(n)
+    in_c, out_c = _calls.rays_struct(rays_in), _calls.rays_struct(outs)
     if dev.type == "cpu":
         from .raytrace import _raise_status_value
 
@@ -356,7 +346,7 @@ def trace_sequential_polarized(lens, rays_in, mode, state, rec=None, want_p=True
         opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
         rc = lib.ort_host_trace_sequential_polarized(
             C.byref(lens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-            None if rec is None else rec.data_ptr(), None, status.ctypes.data, C.byref(pol))
+            addr(rec), None, addr(status), C.byref(pol))
         _native.check(rc, "ort_host_trace_sequential_polarized")
         _raise_status_value(int(status[0]))
         return outs, planes
@@ -367,8 +357,7 @@ def trace_sequential_polarized(lens, rays_in, mode, state, rec=None, want_p=True
         opt.start_surface = start_surface
         rc = lib.ort_trace_sequential_polarized(
             C.byref(lens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-            raytrace._ptr(rec), raytrace._ptr(stats), raytrace._ptr(status), C.byref(pol),
-            stream)
+            addr(rec), addr(stats), addr(status), C.byref(pol), stream)
         _native.check(rc, "ort_trace_sequential_polarized")
 
     raytrace._run(lens, launch, n, max(n, 1), [], newton_mode)
@@ -463,12 +452,9 @@ def _generate(lens, segs, px, py, rays0, n, seg_len, pupil_per_ray):
         raytrace.generate_rays(segs, px, py, rays0, n, seg_len, pupil_per_ray, apod=lens.apod)
         return
     seg = _bytes_tensor(np.asarray(segs, dtype=_abi.SEGMENT))
-    apod = _apod_of(lens)
-    batch = _native.ort_batch(n, max(seg_len, 1), max(n, 1),
-                              seg.numel() // _abi.SEGMENT.itemsize, int(pupil_per_ray),
-                              seg.data_ptr())
-    batch.apod = None if apod is None else apod.data_ptr()
+    apod = _apod_of(lens)  # (kept alive through the call: the struct holds its address)
+    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
     out_c = rays0.c_struct()
-    rc = _native.load_host().ort_host_generate_rays(px.data_ptr(), py.data_ptr(),
-                                                    C.byref(out_c), C.byref(batch))
+    rc = _native.load_host().ort_host_generate_rays(addr(px), addr(py), C.byref(out_c),
+                                                    C.byref(batch))
     _native.check(rc, "ort_host_generate_rays")

@@ -21,7 +21,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, _native, autodiff
+from . import _abi, _calls, _native, autodiff
+from ._calls import addr
 from .pupil import pupil_arrays
 from .lowering import (LensTable, lower_apodization, lower_surface_group, pupil_scalars,
                        segment_params)
@@ -56,12 +57,9 @@ def get_device():
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _addr(t):
-    """A device tensor's address for a c_void_p struct field (None: NULL)."""
-    return t.data_ptr() if t is not None else None
+    """_calls.addr as a c_void_p object (the package passes the int; tests and tools/ that
+    call the library by hand import this)."""
+    return C.c_void_p(addr(t))
 
 
 def _stream_handle():
@@ -112,7 +110,7 @@ class RealRays:
         return self.x.numel()
 
     def c_struct(self):
-        return _native.ort_rays(*(getattr(self, a).data_ptr() for a in _abi.RAY_FIELDS))
+        return _calls.rays_struct([getattr(self, a) for a in _abi.RAY_FIELDS])
 
     def numpy(self):
         return {a: getattr(self, a).detach().cpu().numpy() for a in (*_abi.RAY_FIELDS, "w")}
@@ -246,12 +244,12 @@ class DeviceLens:
                 dtype=torch.int64, device=self.device)
             self._patch_ptrs[pkey] = ptrs
         if ptrs is not None:
-            rc = lib.ort_patch_zernike_ptrs(C.byref(self.c), _ptr(ptrs), _ptr(idx), n,
+            rc = lib.ort_patch_zernike_ptrs(C.byref(self.c), addr(ptrs), addr(idx), n,
                                             _stream_handle())
             _native.check(rc, "ort_patch_zernike_ptrs")
             return
         c = vals[0].contiguous() if len(vals) == 1 else torch.cat(vals)
-        rc = lib.ort_patch_zernike(C.byref(self.c), _ptr(c), _ptr(idx), n, _stream_handle())
+        rc = lib.ort_patch_zernike(C.byref(self.c), addr(c), addr(idx), n, _stream_handle())
         _native.check(rc, "ort_patch_zernike")
 
     # -- Newton schedule speculate / verify ---------------------------------------------
@@ -571,20 +569,20 @@ def _run_device(dlens: DeviceLens, launch, n_rays, group_len, keys, need_status,
                     opt.sched_out = slots[(cur + r) % 2].data_ptr()
                 rounds.append((None, opt, stats[r], status[r]))
             last = slots[(cur + R) % 2]
-            final = (_ptr(stats), _ptr(last), _ptr(flags), _ptr(status), _ptr(small[2 * R + 2]))
+            final = (addr(stats), addr(last), addr(flags), addr(status), addr(small[2 * R + 2]))
         else:
             for r in range(R + 1):
                 fix = None
                 if r > 0:
-                    fix = (_ptr(stats[r - 1]), _ptr(sched_dev),
-                           _ptr(None if r == 1 else flags[r - 2]), _ptr(flags[r - 1]),
-                           _ptr(stats[r]), _ptr(status[r]))
+                    fix = (addr(stats[r - 1]), addr(sched_dev),
+                           addr(None if r == 1 else flags[r - 2]), addr(flags[r - 1]),
+                           addr(stats[r]), addr(status[r]))
                 opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, sched_dev.data_ptr(), 0,
                                           0 if r == 0 else _abi.OPT_NO_INIT,
                                           None if r == 0 else flags[r - 1].data_ptr())
                 rounds.append((fix, opt, stats[r], status[r]))
             last = sched_dev
-            final = (_ptr(stats[R]), _ptr(last), _ptr(flags[R - 1]), _ptr(flags[R]))
+            final = (addr(stats[R]), addr(last), addr(flags[R - 1]), addr(flags[R]))
         plan = (rounds, final, last, (cur + R) % 2 if fused else cur)
         dlens._async_plans[(kk, R, cur)] = plan
     rounds, final, last, new_cur = plan
@@ -605,13 +603,13 @@ def _run_device(dlens: DeviceLens, launch, n_rays, group_len, keys, need_status,
         if rms is not None:
             part, rows, stats_t, rms_t = rms
             rc = lib.ort_newton_finish_rms(lens_c, n_groups, final[0], R, 0, final[1],
-                                           final[2], final[3], final[4], _ptr(sched_copy),
-                                           _ptr(part), rows, _ptr(stats_t), _ptr(rms_t),
+                                           final[2], final[3], final[4], addr(sched_copy),
+                                           addr(part), rows, addr(stats_t), addr(rms_t),
                                            stream)
             rms = None
         else:
             rc = lib.ort_newton_finish(lens_c, n_groups, final[0], R, 0, final[1], final[2],
-                                       final[3], final[4], _ptr(sched_copy), stream)
+                                       final[3], final[4], addr(sched_copy), stream)
         _native.check(rc, "ort_newton_finish")
     else:
         sched_copy = None
@@ -650,7 +648,7 @@ def _run_device(dlens: DeviceLens, launch, n_rays, group_len, keys, need_status,
 
 def _rms_finish(lib, rms, stream):
     part, rows, stats_t, rms_t = rms
-    rc = lib.ort_rms_finish(_ptr(part), rows, _ptr(stats_t), _ptr(rms_t), stream)
+    rc = lib.ort_rms_finish(addr(part), rows, addr(stats_t), addr(rms_t), stream)
     _native.check(rc, "ort_rms_finish")
 
 
@@ -766,21 +764,18 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
     lib = _native.load()
     seg_dev = (segments if torch.is_tensor(segments) else
                dlens.resident("segments", np.asarray(segments, dtype=_abi.SEGMENT)))
-    n_seg = seg_dev.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n_rays, seg_len, group_len, n_seg, int(pupil_per_ray),
-                              seg_dev.data_ptr())
-    batch.apod = _addr(dlens.apod)
+    batch = _calls.pupil_batch(n_rays, seg_len, group_len, seg_dev, pupil_per_ray, dlens.apod)
     out_c = out.c_struct()
     stream = _stream_handle()  # one stream for all the launches of this call
-    args = (C.byref(dlens.c), _ptr(px), _ptr(py), C.byref(out_c), C.byref(batch))
-    rec_p, tape_p = _ptr(rec), _addr(tape)
+    args = (C.byref(dlens.c), addr(px), addr(py), C.byref(out_c), C.byref(batch))
+    rec_p, tape_p = addr(rec), addr(tape)
     rows = -(-int(n_rays) // 256)  # one row per trace workgroup (kBlock)
     part = None
     if rms is not None:
         if tape is None:
             raise ValueError("trace_pupil: the fused rms spot size needs the taped forward")
         part = torch.empty(rows * 4, dtype=torch.float64, device=dlens.device)
-    part_p = _addr(part)
+    part_p = addr(part)
 
     def launch(opt, stats, status):
         opt.start_surface = start_surface
@@ -788,7 +783,7 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
         opt.rms_part = part_p
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
-        rc = lib.ort_trace_pupil(*args, C.byref(opt), rec_p, _ptr(stats), _ptr(status), stream)
+        rc = lib.ort_trace_pupil(*args, C.byref(opt), rec_p, addr(stats), addr(status), stream)
         _native.check(rc, "ort_trace_pupil")
 
     _run(dlens, launch, n_rays, group_len, list(keys), newton_mode,
@@ -806,14 +801,12 @@ def trace_spot(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays, seg_l
     lib = _native.load()
     seg_dev = (segments if torch.is_tensor(segments) else
                dlens.resident("segments", np.asarray(segments, dtype=_abi.SEGMENT)))
-    n_seg = seg_dev.numel() // _abi.SEGMENT.itemsize
-    batch = _native.ort_batch(n_rays, seg_len, seg_len, n_seg, 0, seg_dev.data_ptr())
-    batch.apod = _addr(dlens.apod)
+    batch = _calls.pupil_batch(n_rays, seg_len, seg_len, seg_dev, False, dlens.apod)
     out_c = out.c_struct()
 
     def launch(opt, stats, status):
-        rc = lib.ort_trace_spot(C.byref(dlens.c), _ptr(px), _ptr(py), C.byref(out_c),
-                                C.byref(batch), C.byref(opt), _ptr(status), C.byref(spot._lay),
+        rc = lib.ort_trace_spot(C.byref(dlens.c), addr(px), addr(py), C.byref(out_c),
+                                C.byref(batch), C.byref(opt), addr(status), C.byref(spot._lay),
                                 C.c_void_p(spot._ws.data_ptr()), spot._size,
                                 C.c_void_p(spot.out.data_ptr()), _stream_handle())
         _native.check(rc, "ort_trace_spot")
@@ -832,24 +825,13 @@ def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_l
     lib = _native.load()
     n = len(rays_in)
     group_len = group_len or max(n, 1)
-    seg_dev = None
-    if segments is not None:
-        seg_dev = _to_device_bytes(segments, dlens.device)
-        batch = _native.ort_batch(n, seg_len, group_len, len(segments), 0, seg_dev.data_ptr())
-    else:
-        batch = _native.ort_batch(n, max(n, 1), group_len, 0, 0, None)
+    seg_dev = None if segments is None else _to_device_bytes(segments, dlens.device)
+    batch = _calls.resident_batch(n, group_len, seg_dev, seg_len)
     w_keep = None
     if per_ray_w:
-        w_keep = rays_in.w.to(device=dlens.device, dtype=torch.float64).reshape(-1)
-        w_keep = w_keep.expand(n).contiguous() if w_keep.numel() == 1 else w_keep.contiguous()
-        if w_keep.numel() != n:
-            raise ValueError("rays.w must hold one wavelength per ray")
-        mt = dlens.table.mat_table
-        if mt is not None and np.any(mt["kind"] == _abi.MAT_ABBE):
-            # abbe.py:47-48 raises before any n is used; the device would only give NaN
-            if bool(((w_keep < 0.380) | (w_keep > 0.750)).any()):
-                raise ValueError("Wavelength out of range for this model.")
-        batch.w = w_keep.data_ptr()
+        w_keep = _calls.per_ray_wavelengths(dlens.table, rays_in.w, n, dlens.device,
+                                            validate=True)
+        batch.w = addr(w_keep)
     in_c, out_c = rays_in.c_struct(), rays_out.c_struct()
 
     def launch(opt, stats, status):
@@ -857,8 +839,8 @@ def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_l
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
         rc = lib.ort_trace_sequential(C.byref(dlens.c), C.byref(in_c), C.byref(out_c),
-                                      C.byref(batch), C.byref(opt), _ptr(rec), _ptr(stats),
-                                      _ptr(status), _stream_handle())
+                                      C.byref(batch), C.byref(opt), addr(rec), addr(stats),
+                                      addr(status), _stream_handle())
         _native.check(rc, "ort_trace_sequential")
 
     if rays_in is rays_out and dlens.newton and newton_mode != "wave":
@@ -878,11 +860,9 @@ def generate_rays(segments, px, py, out: RealRays, n_rays, seg_len, pupil_per_ra
     (DeviceLens.apod) or None."""
     lib = _native.load()
     seg_dev = _to_device_bytes(segments, out.x.device)
-    batch = _native.ort_batch(n_rays, seg_len, n_rays, len(segments), int(pupil_per_ray),
-                              seg_dev.data_ptr())
-    batch.apod = _addr(apod)
+    batch = _calls.pupil_batch(n_rays, seg_len, n_rays, seg_dev, pupil_per_ray, apod)
     out_c = out.c_struct()
-    rc = lib.ort_generate_rays(_ptr(px), _ptr(py), C.byref(out_c), C.byref(batch),
+    rc = lib.ort_generate_rays(addr(px), addr(py), C.byref(out_c), C.byref(batch),
                                _stream_handle())
     _native.check(rc, "ort_generate_rays")
     return seg_dev
@@ -1244,8 +1224,8 @@ def geometry_sag_normal(geometry, x, y):
     n = xs.numel()
     out = [torch.empty(n, dtype=torch.float64, device=dev) for _ in range(4)]
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = lib.ort_surface_sag_normal(C.byref(dl.c), 0, _ptr(xs), _ptr(ys), n,
-                                    *(_ptr(o) for o in out), _ptr(status), _stream_handle())
+    rc = lib.ort_surface_sag_normal(C.byref(dl.c), 0, addr(xs), addr(ys), n,
+                                    *(addr(o) for o in out), addr(status), _stream_handle())
     _native.check(rc, "ort_surface_sag_normal")
     _raise_status(status)
     return tuple(out)
@@ -1261,7 +1241,7 @@ def geometry_distance(geometry, rays):
 
     def launch(opt, stats, status):
         rc = lib.ort_surface_distance(C.byref(dl.c), 0, C.byref(rays_c), n, C.byref(opt),
-                                      _ptr(t), _ptr(stats), _ptr(status), _stream_handle())
+                                      addr(t), addr(stats), addr(status), _stream_handle())
         _native.check(rc, "ort_surface_distance")
 
     _run(dl, launch, n, max(n, 1), [("distance", n)])
@@ -1275,7 +1255,7 @@ def material_nk(dlens: DeviceLens, mat: int, w):
     w = _as_device(w, dlens.device)
     n_out = torch.empty_like(w)
     k_out = torch.empty_like(w)
-    rc = lib.ort_material_nk(C.byref(dlens.c), int(mat), _ptr(w), w.numel(), _ptr(n_out),
-                             _ptr(k_out), _stream_handle())
+    rc = lib.ort_material_nk(C.byref(dlens.c), int(mat), addr(w), w.numel(), addr(n_out),
+                             addr(k_out), _stream_handle())
     _native.check(rc, "ort_material_nk")
     return n_out, k_out
