@@ -57,6 +57,48 @@ def resident_batch(n, group_len=None, seg=None, seg_len=None):
     return _batch(n, seg_len or max(n, 1), group_len or max(n, 1), seg, False, None)
 
 
+def decreasing_tables(table):
+    """{material index: name} of the lens materials with tabulated n or k data whose
+    wavelengths decrease somewhere (45 of the refractiveindex.info database's 2,631 tables
+    are not strictly increasing; repeated wavelengths are fine, a decreasing step is not).
+    Found once per LensTable."""
+    hit = getattr(table, "_decreasing_tables", None)
+    if hit is not None:
+        return hit
+    hit = {}
+    mt = table.mat_table
+    for mi in range(0 if mt is None else len(mt)):
+        m = mt[mi]
+        spans = [(int(m["k_off"]), int(m["k_len"]))]
+        if int(m["kind"]) == _abi.MAT_TABULATED:
+            spans.append((int(m["coef_off"]), int(m["n_coef"])))
+        if any(np.any(np.diff(table.coef[o:o + ln]) < 0) for o, ln in spans if ln > 1):
+            mats = getattr(table, "materials", None) or []
+            m = mats[mi] if mi < len(mats) else None
+            if m is None:
+                hit[mi] = f"material {mi}"
+            else:  # a wrapped reference material has no repr of its own: its file instead
+                own = type(m).__repr__ is not object.__repr__
+                hit[mi] = repr(m) if own else str(m.key())
+    table._decreasing_tables = hit
+    return hit
+
+
+def refuse_decreasing_tables(table, mats=None):
+    """Per-ray wavelengths (ort_batch.w, ort_material_nk) through a table whose wavelengths
+    decrease are refused: numpy.interp, which the reference calls, searches such a table
+    from the index its previous query found, so its value depends on the order of the
+    queries -- nothing a per-ray kernel can reproduce (csrc/ort_material.h np_interp). The
+    per-wavelength n / alpha tables are host NumPy and stay available. mats: only these
+    material indices (None: every material of the lens)."""
+    bad = decreasing_tables(table)
+    names = [v for k, v in bad.items() if mats is None or k in mats]
+    if names:
+        raise ValueError(f"{', '.join(names)}: the tabulated wavelengths decrease, so "
+                         "numpy.interp depends on the query order; per-ray wavelengths are "
+                         "refused for this material (per-wavelength tables still work).")
+
+
 def per_ray_wavelengths(table, w, n, device, validate):
     """ort_batch.w: `w` as n contiguous float64 wavelengths on `device` (one value: expanded;
     already so: the same memory, no copy). The caller keeps the result alive until its
@@ -66,7 +108,11 @@ def per_ray_wavelengths(table, w, n, device, validate):
     such a material, as the reference does before it uses any index (abbe.py:47-48; the
     device would only give NaN). That reads `w` -- a device synchronisation -- so the
     forward traces validate and the VJPs do not: a backward's `w` is the one its forward
-    checked. This is the one intended difference between the call sites."""
+    checked. This is the one intended difference between the call sites.
+
+    Every call site refuses a lens with a decreasing wavelength table
+    (refuse_decreasing_tables; host data only, no synchronisation)."""
+    refuse_decreasing_tables(table)
     w = w.detach().to(device=device, dtype=torch.float64).reshape(-1)
     w = w.expand(n).contiguous() if w.numel() == 1 else w.contiguous()
     if w.numel() != n:

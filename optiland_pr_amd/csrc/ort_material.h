@@ -18,13 +18,17 @@ ORT_INLINE double wpow(double w, double e) {
   return e == 2.0 ? w * w : ::pow(w, e);
 }
 
-// numpy.interp(x, xp, fp) for increasing xp (numpy/_core/src/multiarray/compiled_base.c
-// arr_interp): clamped ends, exact hits, slope * (x - xp[j]) + fp[j] with its NaN fallbacks
+// numpy.interp(x, xp, fp) for non-decreasing xp (numpy/_core/src/multiarray/compiled_base.c
+// arr_interp): clamped ends, exact hits, slope * (x - xp[j]) + fp[j] with its NaN fallbacks.
+// j is the LAST knot <= x, so a repeated wavelength gives the value of its last entry --
+// at xp[0] too, which is why only x < xp[0] takes the left clamp. Tables whose wavelengths
+// decrease somewhere never come here: the host refuses them (materials.decreasing_table),
+// since numpy's search of an unsorted xp depends on the order of the queries.
 template <class PD>
 ORT_INLINE double np_interp(double x, PD xp, PD fp, int n) {
   if (n == 1) return fp[0];  // one point: fp[0] everywhere (NaN included)
   if (x != x) return x;
-  if (x <= xp[0]) return fp[0];
+  if (x < xp[0]) return fp[0];
   if (x >= xp[n - 1]) return fp[n - 1];
   int lo = 0, hi = n - 1;  // xp[lo] <= x < xp[hi]
   while (hi - lo > 1) {

@@ -92,8 +92,10 @@ class IdealMaterial(BaseMaterial):
 class Material(BaseMaterial):
     """Catalog glass (materials/material.py:22-75 + material_file.py:31-428).
 
-    Only glasses baked into data/glasses.json are available (the sample lenses'
+    By name, only glasses baked into data/glasses.json are available (the sample lenses'
     glasses); other names raise ValueError, as the reference does for an unknown name.
+    Any other refractiveindex.info material comes in as a record of the same fields
+    through Material.from_entry.
     """
 
     def __init__(self, name: str, reference: str | None = None):
@@ -105,16 +107,30 @@ class Material(BaseMaterial):
             if not cands:
                 raise ValueError(f"No matching material found for {name!r} ({reference!r}).")
             key = cands[0]
-        e = db[key]
+        self._set_entry(db[key])
+
+    @classmethod
+    def from_entry(cls, entry):
+        """A Material from a record with the fields of a data/glasses.json entry: name,
+        reference, source (the file's path in the database: the material's identity,
+        key()), formula ("formula 1" .. "formula 9", "tabulated n", "tabulated nk"),
+        coefficients as the file lists them, and the k_wavelength / k and n_wavelength / n
+        tables (None where the file has none)."""
+        m = cls.__new__(cls)
+        m._set_entry(entry)
+        return m
+
+    def _set_entry(self, e):
+        arr = lambda v: None if v is None else np.array(v, dtype=np.float64)  # noqa: E731
         self.name = e["name"]
-        self.reference = e["reference"]
+        self.reference = e.get("reference")
         self.source = e["source"]
         self._n_formula = e["formula"]
-        self.coefficients = None if e["coefficients"] is None else np.array(e["coefficients"])
-        self._k_wavelength = None if e["k_wavelength"] is None else np.array(e["k_wavelength"])
-        self._k = None if e["k"] is None else np.array(e["k"])
-        self._n_wavelength = None if e.get("n_wavelength") is None else np.array(e["n_wavelength"])
-        self._n = None if e.get("n") is None else np.array(e["n"])
+        self.coefficients = arr(e.get("coefficients"))
+        self._k_wavelength = arr(e.get("k_wavelength"))
+        self._k = arr(e.get("k"))
+        self._n_wavelength = arr(e.get("n_wavelength"))
+        self._n = arr(e.get("n"))
 
     def key(self):
         return ("glass", self.source)

@@ -1250,8 +1250,10 @@ def geometry_distance(geometry, rays):
 
 def material_nk(dlens: DeviceLens, mat: int, w):
     """(n, k) of lens material `mat` at device wavelengths w (ort_material_nk): the per-ray
-    dispersion the kernels evaluate when rays carry their own wavelengths."""
+    dispersion the kernels evaluate when rays carry their own wavelengths. A material whose
+    tabulated wavelengths decrease is refused (_calls.refuse_decreasing_tables)."""
     lib = _native.load()
+    _calls.refuse_decreasing_tables(dlens.table, [int(mat)])
     w = _as_device(w, dlens.device)
     n_out = torch.empty_like(w)
     k_out = torch.empty_like(w)

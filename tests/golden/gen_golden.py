@@ -983,6 +983,214 @@ def mixed_wavelength_goldens():
     np.savez_compressed(os.path.join(HERE, "mixed_w.npz"), **out)
 
 
+# One or more real materials per branch of csrc/ort_material.h (paths in the reference's
+# database, without ".yml"). main/Ag/Yang and glass/hikari/CaF/NICF-A repeat a wavelength;
+# glass/lzos/CTK8 has a decreasing step.
+DISPERSION_MATERIALS = (
+    "organic/(C5H8O2)n - poly(methyl methacrylate)/Bodurov",  # formula 1
+    "main/Ag3AsS3/Hulme-e", "main/AgCl/Tilton", "main/AgGaS2/Kato-e",  # formula 4: 9/11/13
+    "glass/misc/soda-lime/Rubin-clear",  # formula 5 + k table
+    "main/Ar/Peck-0C", "main/Ar/Bideau-Mehu",  # formula 6: 3 / 7 coefficients
+    "main/Si/Edwards",  # formula 7
+    "main/AgBr/Schroter",  # formula 8
+    "organic/CH4N2O - urea/Rosker-e",  # formula 9
+    "glass/barberini/D0082", "other/commercial plastics/CR-39/mono",  # tabulated n
+    "glass/ami/AMTIR-1", "glass/lightpath/BD6",  # tabulated nk
+    "glass/hikari/CaF/NICF-A", "main/Ag/Yang",  # repeated wavelengths
+    "glass/lzos/CTK8",  # a decreasing step
+    # formula 4 with 9 coefficients (no tail) and a non-zero second pole term: the three
+    # formula-4 files above all have C5 = 0, which hides that term
+    "main/CdS/Bieniewski-e",
+)
+# The singlet of the dispersion traces (tests/_dispersion.py restates it with the native
+# API): object at infinity, two spherical surfaces in air, stop on the first; the Newton
+# variant turns the second surface into an even asphere.
+DISPERSION_SINGLET = dict(r1=40.0, t1=4.0, r2=-60.0, t2=30.0,
+                          asphere=[1e-4, -2e-6, 1e-8])
+DISPERSION_NEWTON = ("organic/(C5H8O2)n - poly(methyl methacrylate)/Bodurov",
+                     "main/AgCl/Tilton", "glass/ami/AMTIR-1", "main/Ar/Bideau-Mehu")
+
+
+def _mp_dispersion(formula, coef, xp, fp, w):
+    """n(w) of one refractiveindex.info record in mpmath at 60 digits from the raw
+    coefficients (the doubles of the file), rounded to double; NaN where the value is not
+    a finite real number. Tables: the exact linear interpolant on numpy.interp's segment
+    (the last knot <= w), its clamped ends and exact knots."""
+    import mpmath as mp
+
+    mp.mp.dps = 60
+    out = np.full(w.shape, np.nan)
+    if formula.startswith("tabulated"):
+        X, F = [mp.mpf(float(v)) for v in xp], [mp.mpf(float(v)) for v in fp]
+        for i, wv in enumerate(w):
+            if len(xp) == 1 or wv < xp[0]:
+                out[i] = fp[0]
+            elif wv >= xp[-1]:
+                out[i] = fp[-1]
+            else:
+                j = int(np.searchsorted(xp, wv, side="right")) - 1
+                x = mp.mpf(float(wv))
+                out[i] = float(F[j] if X[j] == x else
+                               F[j] + (F[j + 1] - F[j]) / (X[j + 1] - X[j]) * (x - X[j]))
+        return out
+    fid = int(formula.split()[-1])
+    c = [mp.mpf(float(v)) for v in coef]
+    for i, wv in enumerate(w):
+        x = mp.mpf(float(wv))
+        try:
+            if fid in (1, 2):
+                n = 1 + c[0]
+                for k in range(1, len(c), 2):
+                    n += c[k] * x**2 / (x**2 - (c[k + 1] ** 2 if fid == 1 else c[k + 1]))
+                n = mp.sqrt(n)
+            elif fid in (3, 5):
+                n = c[0]
+                for k in range(1, len(c), 2):
+                    n += c[k] * x ** c[k + 1]
+                n = mp.sqrt(n) if fid == 3 else n
+            elif fid == 4:
+                n = (c[0] + c[1] * x ** c[2] / (x**2 - c[3] ** c[4])
+                     + c[5] * x ** c[6] / (x**2 - c[7] ** c[8]))
+                for k in range(9, len(c), 2):
+                    n += c[k] * x ** c[k + 1]
+                n = mp.sqrt(n)
+            elif fid == 6:
+                n = 1 + c[0]
+                for k in range(1, len(c), 2):
+                    n += c[k] / (c[k + 1] - x**-2)
+            elif fid == 7:
+                d = x**2 - mp.mpf(0.028)  # the double 0.028, as the reference has it
+                n = c[0] + c[1] / d + c[2] / d**2
+                for k in range(3, len(c)):
+                    n += c[k] * x ** (2 * (k - 2))
+            elif fid == 8:
+                b = c[0] + c[1] * x**2 / (x**2 - c[2]) + c[3] * x**2
+                n = mp.sqrt((1 + 2 * b) / (1 - b))
+            elif fid == 9:
+                n = mp.sqrt(c[0] + c[1] / (x**2 - c[2])
+                            + c[3] * (x - c[4]) / ((x - c[4]) ** 2 + c[5]))
+            else:
+                raise ValueError(formula)
+        except ZeroDivisionError:
+            continue
+        if isinstance(n, mp.mpf) and mp.isfinite(n):
+            out[i] = float(n)
+    return out
+
+
+def _dispersion_singlet(material, asphere):
+    s = DISPERSION_SINGLET
+    lens = ref_optic.Optic()
+    lens.add_surface(index=0, radius=np.inf, thickness=np.inf)
+    lens.add_surface(index=1, radius=s["r1"], thickness=s["t1"], material=material,
+                     is_stop=True)
+    kw = dict(surface_type="even_asphere", conic=0.0, coefficients=s["asphere"]) if asphere else {}
+    lens.add_surface(index=2, radius=s["r2"], thickness=s["t2"], **kw)
+    lens.add_surface(index=3)
+    return lens
+
+
+def _dispersion_trace(out, prefix, fn, lo, hi, rng, asphere):
+    """SurfaceGroup.trace of 256 rays with 256 distinct wavelengths inside [lo, hi] through
+    the singlet of MaterialFile(fn). The ray heights are halved until no ray is clipped or
+    totally reflected in the reference (a metal's n << 1 reflects all but near-normal
+    rays); that is asserted here, not in the tests."""
+    from optiland.materials.material_file import MaterialFile
+    from optiland.rays import RealRays
+
+    n = 256
+    if lo == hi:  # a one-point table states no interval: n is its constant everywhere
+        lo, hi = 0.9 * lo, 1.1 * hi
+    w = rng.uniform(lo, hi, n)
+    assert np.unique(w).size == n and lo <= w.min() and w.max() <= hi
+    u = rng.uniform(-1, 1, (4, n))
+    scale = 2.0
+    while True:
+        x, y = scale * u[0], scale * u[1]
+        L, M = 0.005 * scale * u[2], 0.005 * scale * u[3]
+        ins = [x, y, np.full(n, -5.0), L, M, np.sqrt(1 - L * L - M * M), np.ones(n)]
+        r = RealRays(*(v.copy() for v in ins), w.copy())
+        with np.errstate(all="ignore"):
+            _dispersion_singlet(MaterialFile(fn), asphere).surface_group.trace(r)
+        res = {a: np.array(getattr(r, a), dtype=np.float64) for a in
+               ("x", "y", "z", "L", "M", "N", "i", "opd")}
+        if all(np.all(np.isfinite(v)) for v in res.values()):
+            break
+        scale /= 2
+        assert scale > 1e-3, prefix
+    for a, v in zip(("x", "y", "z", "L", "M", "N", "i"), ins):
+        out[f"{prefix}/in_{a}"] = v
+    out[f"{prefix}/w"] = w
+    for a, v in res.items():
+        out[f"{prefix}/{a}"] = v
+
+
+def dispersion_goldens():
+    """tests/golden/dispersion_materials.json (data only: the records of
+    DISPERSION_MATERIALS with the fields of a data/glasses.json entry) and dispersion.npz:
+    per material `n/<source>/w` (157 points over 0.9x .. 1.1x of the file's range -- of its
+    table where it states none -- plus, for every table the file has, each knot, both
+    floating-point neighbours of each knot and the two end knots; SORTED ASCENDING, which
+    matters to numpy.interp where the knots decrease), the reference's `n`, `k` there
+    (NaN / inf where it gives them), `n_exact` (_mp_dispersion) and `n_err_ref` =
+    max |n - n_exact| / |n_exact| over the finite points (both absent for the decreasing
+    table, which has no well-defined interpolant); and `trace/<source>/...`,
+    `trace_asph/<source>/...` (_dispersion_trace; none for the decreasing table)."""
+    import optiland
+    import yaml
+    from optiland.materials.material_file import MaterialFile
+
+    db = os.path.join(os.path.dirname(optiland.__file__), "database", "data-nk")
+    entries, out = {}, {}
+    rng = np.random.default_rng(2024)
+    lst = lambda v: None if v is None else [float(x) for x in np.ravel(v)]  # noqa: E731
+    for src in DISPERSION_MATERIALS:
+        fn = os.path.join(db, *src.split("/")) + ".yml"
+        m = MaterialFile(fn)
+        with open(fn) as f:
+            blocks = yaml.safe_load(f)["DATA"]
+        rng_txt = [b["wavelength_range"] for b in blocks if "wavelength_range" in b]
+        tables = [t for t in (m._n_wavelength, m._k_wavelength) if t is not None]
+        if rng_txt:
+            lo, hi = (float(v) for v in str(rng_txt[0]).split())
+        else:
+            lo, hi = float(np.min(tables[0])), float(np.max(tables[0]))
+        entries[src] = dict(
+            name=src.split("/")[-1], reference=None, source=src + ".yml",
+            formula=m._n_formula, wavelength_range=[lo, hi],
+            coefficients=lst(m.coefficients) if len(m.coefficients) else None,
+            k_wavelength=lst(m._k_wavelength), k=lst(m._k),
+            n_wavelength=lst(m._n_wavelength), n=lst(m._n))
+        pts = [np.linspace(0.9 * lo, 1.1 * hi, 157)]
+        for t in tables:
+            t = np.asarray(t, dtype=np.float64)
+            pts += [t, np.nextafter(t, -np.inf), np.nextafter(t, np.inf), t[[0, -1]]]
+        w = np.sort(np.concatenate(pts))  # ascending
+        with np.errstate(all="ignore"):
+            n_ref = np.asarray(m.n(w), dtype=np.float64) * np.ones_like(w)
+            k_ref = np.asarray(m.k(w), dtype=np.float64) * np.ones_like(w)
+        out[f"n/{src}/w"], out[f"n/{src}/n"], out[f"n/{src}/k"] = w, n_ref, k_ref
+        decreasing = any(np.any(np.diff(t) < 0) for t in tables)
+        if decreasing:
+            continue
+        exact = _mp_dispersion(m._n_formula, lst(m.coefficients), m._n_wavelength, m._n, w)
+        # the exact value is finite exactly where the reference's is (NaN: a negative
+        # radicand, inf: a pole), apart from overflow neither has
+        assert np.array_equal(np.isfinite(exact), np.isfinite(n_ref)), src
+        ok = np.isfinite(exact)
+        out[f"n/{src}/n_exact"] = exact
+        out[f"n/{src}/n_err_ref"] = np.array(np.max(np.abs(n_ref[ok] - exact[ok])
+                                                    / np.abs(exact[ok])))
+        _dispersion_trace(out, f"trace/{src}", fn, lo, hi, rng, asphere=False)
+        if src in DISPERSION_NEWTON:
+            _dispersion_trace(out, f"trace_asph/{src}", fn, lo, hi, rng, asphere=True)
+        print(f"{src}: {m._n_formula}, {w.size} points, n_err_ref "
+              f"{float(out[f'n/{src}/n_err_ref']):.2e}", file=sys.stderr)
+    with open(os.path.join(HERE, "dispersion_materials.json"), "w") as f:
+        json.dump(entries, f, indent=None, separators=(",", ":"))
+    np.savez_compressed(os.path.join(HERE, "dispersion.npz"), **out)
+
+
 DIST_CASES = [("random", 1000, {"seed": 7}), ("uniform", 33, {}), ("uniform", 128, {}),
               ("hexapolar", 6, {}), ("hexapolar", 17, {}), ("ring", 13, {}),
               ("line_x", 21, {}), ("line_y", 20, {}), ("positive_line_x", 9, {}),
@@ -1060,6 +1268,9 @@ def main():
     if "--mixed-w" in sys.argv:
         mixed_wavelength_goldens()
         return
+    if "--dispersion" in sys.argv:  # dispersion_materials.json + dispersion.npz only
+        dispersion_goldens()
+        return
     if "--apertures" in sys.argv:
         aperture_goldens()
         return
@@ -1108,6 +1319,7 @@ def main():
     distribution_goldens()
     aperture_goldens()
     mixed_wavelength_goldens()
+    dispersion_goldens()
     WAVEFRONT_CASES["finite_pih_03_07"] = (finite_pih,) + WAVEFRONT_CASES["finite_pih_03_07"][1:]
     index["_analysis"] = analysis_goldens()
     wavefront_strategy_goldens()
