@@ -34,6 +34,9 @@ extern "C" {
 
 int ort_host_abi_version(void);
 
+/* lens->frame_flags: ORT_LENS_AXIAL and ORT_LENS_PLAIN (optiland_rt.h) are both
+ * accepted and ignored: the host library has one form of every trace. */
+
 /* ort_trace_sequential on host memory. updates (nullable): int32 [n_groups][n_surfaces],
  * the Newton updates the reference's stop rule made per (group, surface) (0 for closed-form
  * surfaces) -- the schedule ort_host_trace_sequential_vjp replays. opt->sched and

@@ -97,7 +97,17 @@ enum ort_lens_flags {
   /* every surface's frame is a translation along z only: both op lists empty and
    * cs_t[0], cs_t[1] == +0 (a centred axial lens such as every sample objective). The
    * kernels then skip localize's x + -0, y + -0 (identities) and the op-list loops. */
-  ORT_LENS_AXIAL = 1u << 0
+  ORT_LENS_AXIAL = 1u << 0,
+  /* (added without a new version number: a bit of a field whose 0 stays valid and means
+   * "make no assumption", so libraries and callers of either age work together) every
+   * surface is ORT_GEOM_PLANE or ORT_GEOM_STANDARD without ORT_SURF_APERTURE,
+   * ORT_SURF_APERTURE_PROG, ORT_SURF_REFLECTIVE or ORT_SURF_RECORD, and every
+   * ORT_GEOM_STANDARD surface carries ORT_SURF_INV_R2 or ORT_SURF_RADIUS_INF (every sample
+   * objective). Together with ORT_LENS_AXIAL the closed-form kernels then run a fast pass
+   * that reads a short list of each surface's fields and skips the tests such a lens
+   * never passes; the results are the same bits either way. A caller that sets the bit on a lens that does not meet it
+   * gets undefined rays; 0 is always safe. */
+  ORT_LENS_PLAIN = 1u << 1
 };
 
 /* ---- interaction models (optiland/interactions) ----------------------------------

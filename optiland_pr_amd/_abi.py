@@ -63,6 +63,7 @@ SURF_ALPHA_ALL = 1 << 7
 SURF_ALPHA_NONE = 1 << 8
 SURF_SLOPE_INEXACT = 1 << 9  # (v19) the Newton slope is not the sag's derivative
 LENS_AXIAL = 1 << 0  # ort_lens.frame_flags
+LENS_PLAIN = 1 << 1  # planes / conics only, no aperture, mirror or record
 
 # enum ort_interaction / ort_phase_kind
 IA_REFRACT_REFLECT = 0

@@ -68,6 +68,8 @@ enum : uint32_t {
                         // kVerifyGrid workgroups strides over the blocks of rays
   F_POL = 1u << 14,  // coatings / the polarization matrix per ray (ort_polar.h,
                      // ort_trace_*_polarized)
+  F_PLAIN = 1u << 15,  // ORT_LENS_PLAIN: planes and conics only, no aperture, mirror or
+                       // recorded surface (closed-form kernels: the fast pass's plain form)
 };
 // every Newton kind compiled in: the host library's one specialisation (the GPU's per-lens
 // KM specialisations only prune code: the values are the same)
@@ -183,7 +185,7 @@ inline int fill_pol(KArgs& a, const ort_batch* batch, const ort_options* opt,
 }
 
 // KArgs from the C ABI structs (argument checks included) and the kernel feature bits the
-// lens and batch call for (F_KM kinds, F_REC, F_WRAY / F_MONO, F_IA, F_AXIAL).
+// lens and batch call for (F_KM kinds, F_REC, F_WRAY / F_MONO, F_IA, F_AXIAL, F_PLAIN).
 inline int fill_args(KArgs& a, const ort_lens* lens, const ort_batch* batch,
                      const ort_options* opt, double* rec, ort_newton_stat* stats,
                      int32_t* status, uint32_t& feat) {
@@ -261,6 +263,9 @@ inline int fill_args(KArgs& a, const ort_lens* lens, const ort_batch* batch,
     if ((lens->interaction_mask & need_w) && !batch->w && !lens->wavelengths) return ORT_ERR_ARG;
   }
   if (lens->frame_flags & ORT_LENS_AXIAL) feat |= F_AXIAL;
+  // the closed-form kernels' bit alone: a lens with a Newton or interaction surface is not
+  // plain whatever its flags say, and the other kernel families are selected without it
+  if ((lens->frame_flags & ORT_LENS_PLAIN) && (feat & (F_KM | F_IA)) == 0) feat |= F_PLAIN;
   if (opt->newton_mode != ORT_NEWTON_SCHEDULE && opt->newton_mode != ORT_NEWTON_WAVE)
     return ORT_ERR_ARG;
   a.vstats = opt->verify_stats;

@@ -1054,6 +1054,55 @@ __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam,
   return r;
 }
 
+// F_PLAIN: what the fast pass of a plain lens reads of one surface -- 9 of the 44 dwords of
+// ort_surface's record and 4 of the 5 doubles of its optics row (F_MONO; otherwise the row
+// is a per-lane load made where it is used).
+struct PlainSurf {
+  double radius, conic, cs_tz, inv_r2, two_r, one_plus_k, r_sq;
+  double n_pre, u, alpha_pre, u_sq;
+  int32_t geometry, flags;
+};
+// row0: the optics row's first index, uniform_row(lam) * n_surf (F_MONO)
+template <uint32_t FEAT>
+__device__ inline PlainSurf plain_load(const KArgs& a, int row0, int si) {
+  const cptr<ort_surface> s = cst(a.surf) + si;
+  PlainSurf p{};
+  p.radius = s->radius;
+  p.conic = s->conic;
+  p.geometry = s->geometry;
+  p.flags = s->flags;
+  p.cs_tz = s->cs_t[2];
+  p.inv_r2 = s->inv_r2;
+  p.two_r = s->two_r;
+  p.one_plus_k = s->one_plus_k;
+  p.r_sq = s->r_sq;
+  if constexpr ((FEAT & F_MONO) != 0) {
+    const cptr<ort_surface_optics> o = cst(a.optics) + (row0 + si);
+    p.n_pre = o->n_pre;
+    p.u = o->u;
+    p.alpha_pre = o->alpha_pre;
+    p.u_sq = o->u_sq;
+  }
+  return p;
+}
+// the list as the records the surface sequences take (the fields outside it stay unset:
+// the plain form reads none of them)
+__device__ inline void plain_unpack(const PlainSurf& p, ort_surface& s, ort_surface_optics& o) {
+  s.radius = p.radius;
+  s.conic = p.conic;
+  s.geometry = p.geometry;
+  s.flags = p.flags;
+  s.cs_t[2] = p.cs_tz;
+  s.inv_r2 = p.inv_r2;
+  s.two_r = p.two_r;
+  s.one_plus_k = p.one_plus_k;
+  s.r_sq = p.r_sq;
+  o.n_pre = p.n_pre;
+  o.u = p.u;
+  o.alpha_pre = p.alpha_pre;
+  o.u_sq = p.u_sq;
+}
+
 // apod: F_GEN | F_REC with an apodization, the pupil factor of this ray, multiplied into
 // every recorded intensity (the generated ray would carry it from the start,
 // ray_generator.py:91-95); 1 otherwise
@@ -1061,9 +1110,25 @@ template <uint32_t FEAT, bool FAST, class B>
 __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, double wl,
                                        int64_t rid, bool active, B& bad, bool& geom_bad,
                                        double apod = 1.0) {
+  // F_PLAIN (the fast pass only: the exact re-trace stays the generic form, so a flagged
+  // lane's result cannot depend on the bit): every uniform test of the record that a plain
+  // lens never passes is compiled out, and the record is the short list of PlainSurf.
+  constexpr bool kPlain = FAST && (FEAT & F_PLAIN) != 0;
+  static_assert(!kPlain || (FEAT & (F_AXIAL | F_REC | F_WRAY)) == F_AXIAL,
+                "the plain form is the axial, unrecorded, table-wavelength kernels'");
+  int row0 = 0;
+  if constexpr (kPlain && (FEAT & F_MONO) != 0) row0 = uniform_row(lam) * a.n_surf;
   for (int si = a.start_surface; si < a.n_surf; ++si) {
-    const ort_surface s = cst(a.surf)[si];
-    const ort_surface_optics o = surface_optics<FEAT>(a, s, lam, si, wl);
+    ort_surface s;
+    ort_surface_optics o;
+    if constexpr (kPlain) {
+      const PlainSurf p = plain_load<FEAT>(a, row0, si);
+      plain_unpack(p, s, o);
+      if constexpr ((FEAT & F_MONO) == 0) o = optics_at<FEAT>(a, lam, si);
+    } else {
+      s = cst(a.surf)[si];
+      o = surface_optics<FEAT>(a, s, lam, si, wl);
+    }
     if constexpr ((FEAT & F_AXIAL) != 0)
       r.z = r.z + -s.cs_t[2];  // x + -0 and y + -0 are identities
     else
@@ -1083,7 +1148,9 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     } else {
       t = is_plane ? ort::distance_plane(r) : ort::distance_conic(r, s.radius, s.conic, radius_inf);
     }
-    if constexpr (FAST) {
+    if constexpr (kPlain) {
+      // every id is a closed-form one (ORT_LENS_PLAIN): nothing to test
+    } else if constexpr (FAST) {
       // not a closed-form id: a uniform test, left to the exact pass (below)
       ORT_CHK_UNIFORM(bad, s.geometry > ORT_GEOM_STANDARD || s.geometry < ORT_GEOM_PLANE);
     } else if (!is_plane && s.geometry != ORT_GEOM_STANDARD) {  // NaN rays + status
@@ -1099,11 +1166,13 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     ort::propagate(r, t, o.alpha_pre);
 #endif
     ort::add_opd(r, t, o.n_pre);
-    if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
+    if constexpr (!kPlain) {  // a plain lens has no aperture
+      if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
 #ifndef ORT_NO_AP_PROG
-    if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
+      if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
 #endif
-    const bool refl = (s.flags & ORT_SURF_REFLECTIVE) != 0;
+    }
+    const bool refl = !kPlain && (s.flags & ORT_SURF_REFLECTIVE) != 0;  // nor a mirror
 #ifndef ORT_NO_FLAT_FAST
     constexpr bool kFlat = FAST;
 #else
@@ -1115,7 +1184,7 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
       double nx, ny, nz;
       if (is_plane) {
         nx = 0.0; ny = 0.0; nz = 1.0;
-      } else if (s.flags & ORT_SURF_INV_R2) {
+      } else if (kPlain || (s.flags & ORT_SURF_INV_R2)) {  // plain: every finite conic has it
         if constexpr (FAST)
           ort::fast::normal_conic_rcp(r.x, r.y, s, nx, ny, nz, sbad);
         else

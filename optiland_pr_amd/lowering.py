@@ -82,12 +82,21 @@ class LensTable:
     @property
     def frame_flags(self):
         """ort_lens.frame_flags: ORT_LENS_AXIAL when every surface frame is a +z
-        translation (no rotation / reference-cs ops, cs_t[0] = cs_t[1] = +0)."""
+        translation (no rotation / reference-cs ops, cs_t[0] = cs_t[1] = +0);
+        ORT_LENS_PLAIN when every surface is a plane or a conic with no aperture of
+        either kind, not a mirror, not recorded, and every conic carries
+        ORT_SURF_INV_R2 or ORT_SURF_RADIUS_INF."""
         s = self.surfaces
         t = s["cs_t"][:, :2]
         axial = (np.all(s["n_cs_loc"] == 0) and np.all(s["n_cs_glob"] == 0)
                  and np.all(t == 0.0) and not np.any(np.signbit(t)))
-        return _abi.LENS_AXIAL if axial else 0
+        g, f = s["geometry"], s["flags"]
+        barred = (_abi.SURF_APERTURE | _abi.SURF_APERTURE_PROG | _abi.SURF_REFLECTIVE
+                  | _abi.SURF_RECORD)
+        conic = g == _abi.GEOM_STANDARD
+        plain = (np.all((g == _abi.GEOM_PLANE) | conic) and not np.any(f & barred)
+                 and np.all((f[conic] & (_abi.SURF_INV_R2 | _abi.SURF_RADIUS_INF)) != 0))
+        return (_abi.LENS_AXIAL if axial else 0) | (_abi.LENS_PLAIN if plain else 0)
 
     @property
     def interaction_mask(self):

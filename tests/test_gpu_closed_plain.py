@@ -1,0 +1,233 @@
+"""The closed-form kernel's plain form (ORT_LENS_PLAIN -> F_PLAIN: the fast pass of a lens of
+planes and conics without aperture, mirror or recorded surface reads a short list of each
+surface's record and skips the uniform tests such a lens never passes).
+
+Every comparison is bit for bit -- NaN payloads and signed zeros included -- against the
+same launch with ORT_OPT_EXACT (every lane through the generic exact re-trace), and against
+the NumPy oracle (same NaN masks, values and zero signs; the intensity to rtol 1e-12, as
+everywhere in the suite).
+
+The plain instantiations are those of generated rays on axial lenses (F_GEN, F_GEN |
+F_MONO); caller-supplied rays and lenses that are not plain run the generic kernels, which
+the cases on them pin.
+"""
+import numpy as np
+import pytest
+
+from tests._plain_lenses import NOT_PLAIN, PLAIN, build
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+
+    if not t.cuda.is_available():
+        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
+    from optiland_pr_amd import _native
+
+    _native.load()
+    return t
+
+
+def _same_bits(got, exp, what):
+    for a in FIELDS:
+        g, e = np.asarray(got[a]), np.asarray(exp[a])
+        np.testing.assert_array_equal(g.view(np.uint64), e.view(np.uint64), err_msg=f"{what} {a}")
+
+
+def _same_as_oracle(got, ref, what):
+    for a in FIELDS:
+        g, r = np.asarray(got[a]), np.asarray(getattr(ref, a))
+        np.testing.assert_array_equal(np.isnan(g), np.isnan(r), err_msg=f"{what} {a} NaN")
+        ok = ~np.isnan(r)
+        if a == "i":
+            with np.errstate(all="ignore"):
+                np.testing.assert_allclose(g[ok], r[ok], rtol=1e-12, atol=0)
+            continue
+        np.testing.assert_array_equal(g[ok], r[ok], err_msg=f"{what} {a}")
+        np.testing.assert_array_equal(np.signbit(g[ok]), np.signbit(r[ok]),
+                                      err_msg=f"{what} sign of {a}")
+
+
+def _pupil(n, seed=5):
+    """n points of the unit disc; the first is the centre, (+0, -0)."""
+    rng = np.random.default_rng(seed)
+    r, th = np.sqrt(rng.uniform(0, 1, n)), rng.uniform(0, 2 * np.pi, n)
+    px, py = r * np.cos(th), r * np.sin(th)
+    px[0], py[0] = 0.0, -0.0
+    return px, py
+
+
+def _trace_generated(torch, dl, segs, px, py, seg_len, exact):
+    from optiland_pr_amd.raytrace import RealRays, trace_pupil
+
+    n = seg_len * len(segs)
+    out = RealRays.empty(n, 0.55)
+    trace_pupil(dl, np.stack(segs), torch.as_tensor(px, device="cuda"),
+                torch.as_tensor(py, device="cuda"), out, n, seg_len, n, exact_only=exact)
+    torch.cuda.synchronize()
+    return out.numpy()
+
+
+def _oracle_generated(dl, segs, px, py):
+    from oracle import trace_np
+
+    parts = []
+    with np.errstate(all="ignore"):
+        for sg in segs:
+            parts.append(trace_np.trace_segment(
+                dl.table, trace_np.generate_rays(sg, px, py), int(sg["lambda_idx"])).rays)
+    return {a: np.concatenate([getattr(p, a) for p in parts]) for a in FIELDS}
+
+
+class _Ref:
+    def __init__(self, d):
+        self.__dict__.update(d)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+@pytest.mark.parametrize("name", sorted(PLAIN))
+def test_plain_lenses_generated_rays(torch, name, n):
+    """1. The sample objectives lower plain and axial; one wave short of full, full, one
+    lane into the next, and two workgroups."""
+    from optiland_pr_amd import _abi
+    from optiland_pr_amd.lowering import segment_params
+    from optiland_pr_amd.raytrace import lens_for
+
+    lens, wl = build(name)
+    dl = lens_for(lens, [wl])
+    assert dl.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN
+    px, py = _pupil(n)
+    segs = [segment_params(lens, 0.0, 0.7, 0)]
+    fast = _trace_generated(torch, dl, segs, px, py, n, False)
+    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), f"{name} n={n}")
+    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), f"{name} n={n}")
+    assert np.isfinite(fast["x"]).all()
+
+
+@pytest.mark.parametrize("name", sorted(PLAIN))
+def test_every_first_surface(torch, name):
+    """2. start_surface = 0 .. n_surf - 1 on caller-supplied rays placed in front of that
+    surface (the last value traces one surface); rays with -0 coordinates meet the
+    first-surface x + 0.0 rule."""
+    from oracle import trace_np
+    from optiland_pr_amd.raytrace import RealRays, lens_for, trace_rays
+
+    lens, wl = build(name)
+    dl = lens_for(lens, [wl])
+    n = 65
+    rng = np.random.default_rng(3)
+    for start in range(dl.table.n_surfaces):
+        z0 = float(dl.table.surfaces["cs_t"][start, 2]) - 0.25
+        x, y = rng.uniform(-0.5, 0.5, n), rng.uniform(-0.5, 0.5, n)
+        x[:2], y[:2] = (-0.0, 0.0), (0.0, -0.0)
+        L, M = rng.uniform(-0.01, 0.01, n), rng.uniform(-0.01, 0.01, n)
+        L[:2], M[:2] = -0.0, -0.0
+        cols = (x, y, np.full(n, z0), L, M, np.sqrt(1.0 - L * L - M * M))
+        outs = {}
+        for exact in (False, True):
+            rout = RealRays.empty(n, wl)
+            trace_rays(dl, RealRays(*cols, 1.0, wl), rout, start_surface=start, exact_only=exact)
+            torch.cuda.synchronize()
+            outs[exact] = rout.numpy()
+        what = f"{name} start={start}"
+        _same_bits(outs[False], outs[True], what)
+        with np.errstate(all="ignore"):
+            ref = trace_np.trace_segment(
+                dl.table, trace_np.Rays(*(c.copy() for c in cols), np.ones(n)), 0,
+                start=start).rays
+        _same_as_oracle(outs[False], ref, what)
+
+
+@pytest.mark.parametrize("name", sorted(PLAIN))
+def test_every_first_surface_generated(torch, name):
+    """2, on the plain kernels themselves: generated rays from every start_surface, fast
+    against exact (the oracle has no generated rays that start inside the lens)."""
+    from optiland_pr_amd.lowering import segment_params
+    from optiland_pr_amd.raytrace import RealRays, lens_for, trace_pupil
+
+    lens, wl = build(name)
+    dl = lens_for(lens, [wl])
+    n = 65
+    px, py = _pupil(n)
+    seg = np.stack([segment_params(lens, 0.0, 0.0, 0)])
+    pxd, pyd = torch.as_tensor(px, device="cuda"), torch.as_tensor(py, device="cuda")
+    for start in range(dl.table.n_surfaces):
+        outs = {}
+        for exact in (False, True):
+            out = RealRays.empty(n, wl)
+            trace_pupil(dl, seg, pxd, pyd, out, n, n, n, start_surface=start, exact_only=exact)
+            torch.cuda.synchronize()
+            outs[exact] = out.numpy()
+        _same_bits(outs[False], outs[True], f"{name} generated start={start}")
+
+
+def test_three_wavelengths(torch):
+    """3. Three wavelength rows and 64-ray segments (F_MONO: the optics row of a wave is
+    lam * n_surf + si), the last row and the last surface included."""
+    from optiland_pr_amd.lowering import segment_params
+    from optiland_pr_amd.raytrace import lens_for
+
+    lens, _ = build("DoubleGauss")
+    wls = [0.4861, 0.5876, 0.6563]
+    dl = lens_for(lens, wls)
+    px, py = _pupil(64)
+    segs = [segment_params(lens, 0.0, hy, lam) for lam in (0, 1, 2) for hy in (0.0, 1.0)]
+    assert [int(s["lambda_idx"]) for s in segs] == [0, 0, 1, 1, 2, 2]
+    fast = _trace_generated(torch, dl, segs, px, py, 64, False)
+    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, 64, True), "three wavelengths")
+    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), "three wavelengths")
+    # the rows differ: the last wavelength's rays are not the first's
+    assert not np.array_equal(fast["y"][:64], fast["y"][256:320])
+
+
+@pytest.mark.parametrize("case", sorted(NOT_PLAIN))
+def test_lenses_that_are_not_plain(torch, case):
+    """4. One surface each that the plain form cannot trace: the plain kernels' bits
+    (plain and axial together) are not both set, and the trace equals the exact launch
+    and the oracle. A decentred lens is plain by the rule (the rule is about surfaces,
+    not frames) and is kept off the plain kernels by its clear axial bit."""
+    from optiland_pr_amd import _abi
+    from optiland_pr_amd.lowering import segment_params
+    from optiland_pr_amd.raytrace import lens_for
+
+    lens, wl, record = build(case)
+    dl = lens_for(lens, [wl], record=record)
+    if case == "decentred":
+        assert not dl.c.frame_flags & _abi.LENS_AXIAL
+    else:
+        assert not dl.c.frame_flags & _abi.LENS_PLAIN
+    n = 257
+    px, py = _pupil(n)
+    segs = [segment_params(lens, 0.0, 0.0, 0)]
+    fast = _trace_generated(torch, dl, segs, px, py, n, False)
+    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), case)
+    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), case)
+
+
+@pytest.mark.parametrize("name", sorted(PLAIN))
+def test_bit_leaves_results_alone(torch, name):
+    """5. The same lowered lens with ORT_LENS_PLAIN cleared in its flags (the generic
+    kernel) gives the bits it gives with the bit set."""
+    from optiland_pr_amd import _abi
+    from optiland_pr_amd.lowering import segment_params
+    from optiland_pr_amd.raytrace import lens_for
+
+    lens, wl = build(name)
+    dl = lens_for(lens, [wl])
+    n = 4099
+    px, py = _pupil(n)
+    segs = [segment_params(lens, 0.0, 1.0, 0)]
+    on = _trace_generated(torch, dl, segs, px, py, n, False)
+    flags = dl.c.frame_flags
+    assert flags & _abi.LENS_PLAIN
+    dl.c.frame_flags = flags & ~_abi.LENS_PLAIN
+    try:
+        off = _trace_generated(torch, dl, segs, px, py, n, False)
+    finally:
+        dl.c.frame_flags = flags
+    _same_bits(on, off, f"{name} plain bit on / off")
