@@ -96,17 +96,15 @@ def build_host(force=False, verbose=False):
     return HOST_LIB_PATH
 
 
-def build(force=False, verbose=False, out=None, extra_flags=(), jobs=None):
+def build(force=False, verbose=False, jobs=None):
     """Compile every translation unit (in parallel) and link liboptiland_rt.so; the host
-    library liboptiland_host.so is compiled alongside (default output only).
-    out / extra_flags: build a variant library elsewhere (A/B timing)."""
-    host = None if out else _start_host_build(force, verbose)
-    out = out or LIB_PATH
+    library liboptiland_host.so is compiled alongside."""
+    host = _start_host_build(force, verbose)
+    out = LIB_PATH
     if not force and not needs_build(out):
         _finish_host_build(host)
         return out
-    obj_dir = os.path.join(os.path.dirname(out), "obj" + ("" if out == LIB_PATH else "_" +
-                           os.path.splitext(os.path.basename(out))[0]))
+    obj_dir = os.path.join(LIB_DIR, "obj")
     os.makedirs(obj_dir, exist_ok=True)
     cc = hipcc()
     inc = ["-I", os.path.join(REPO, "include")]
@@ -117,7 +115,7 @@ def build(force=False, verbose=False, out=None, extra_flags=(), jobs=None):
     # a translation unit is recompiled when it or a header is newer than its object, or when
     # the flags changed (force: every unit)
     flag_file = os.path.join(obj_dir, "flags.txt")
-    flags_now = " ".join([*HIPCC_FLAGS, *extra_flags])
+    flags_now = " ".join(HIPCC_FLAGS)
     same_flags = os.path.exists(flag_file) and open(flag_file).read() == flags_now
     newest_hdr = max(os.path.getmtime(h) for h in HEADERS)
 
@@ -132,7 +130,7 @@ def build(force=False, verbose=False, out=None, extra_flags=(), jobs=None):
             objs.append(obj)
             if fresh(src, obj):
                 continue
-            cmd = [cc, *HIPCC_FLAGS, *extra_flags, *inc, "-c", "-o", obj, src]
+            cmd = [cc, *HIPCC_FLAGS, *inc, "-c", "-o", obj, src]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             procs.append((subprocess.Popen(cmd), src))

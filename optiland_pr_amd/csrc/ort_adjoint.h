@@ -24,17 +24,12 @@ namespace ortk {
 // scratch) 582-588 us, 4 waves (128 VGPRs, 216 B) 591-595 us -- the compiler's choice is
 // the slowest. Re-measured after the Cartesian Zernike form (177 VGPRs uncapped): 3 waves
 // (168, 24 B) 437 us, 4 waves (128, 164 B) 446-452 us per ort_trace_pupil_vjp sequence.
-// Other kernels keep the compiler's choice. ORT_ADJ_WAVES overrides the target for A/B
-// builds.
+// Other kernels keep the compiler's choice.
 template <uint32_t KM, int P>
 struct AdjWaves {
   static constexpr int value = (P == 2 && (KM & ort::KM_ZERN) != 0 && KM < ort::KM_FREE) ? 3 : 1;
 };
-#ifdef ORT_ADJ_WAVES
-#define ORT_ADJ_OCC __attribute__((amdgpu_waves_per_eu(ORT_ADJ_WAVES)))
-#else
 #define ORT_ADJ_OCC __attribute__((amdgpu_waves_per_eu(AdjWaves<KM, P>::value)))
-#endif
 
 // adj_ray's lane policy on the GPU (ort_sweep.h): one ray per lane; a slot contribution is
 // summed over the wave and stored by lane 0 into partial[slot][wave] (one writer per slot
@@ -44,19 +39,11 @@ struct AdjWaves {
 // Newton replay's dual-number Zernike evaluation; with the plain-double jet that costs
 // more than it saves: 657 vs 591 us at 4 waves, rocprofv3 A/B, so the state stays in
 // registers.)
-// Zernike coefficient contributions: the first kZAcc terms of a surface are added per lane
-// in LDS over the hit point and the (up to kHist) replayed Newton iterates, and summed over
-// the wave once per surface -- one DPP wave sum per term and surface instead of one per
-// term and evaluation (32 KB of LDS per block; TMA 1M rays: 582 -> 551 us per adjoint
-// launch, rocprofv3 A/B). ORT_ADJ_ZACC=0 (A/B builds): a wave sum per evaluation.
-// Round 5: surfaces with a Cartesian block take the monomial-basis slots (mono_put below)
-// and need no per-lane term accumulators; the LDS they took (32 KB per block) held the
-// kernel at 3 blocks per CU, so the per-evaluation wave sums serve the polar surfaces
-// (radial order > 6) by default.
-#ifndef ORT_ADJ_ZACC
-#define ORT_ADJ_ZACC 0
-#endif
-constexpr int kZAcc = ORT_ADJ_ZACC;
+// Zernike coefficient contributions of the polar surfaces (radial order > 6) take a wave
+// sum per term and evaluation (emit). Per-lane LDS accumulators summed once per surface
+// (TMA 1M rays: 582 -> 551 us per adjoint launch in round 4) cost 32 KB of LDS per block,
+// which held the kernel at 3 blocks per CU once the surfaces with a Cartesian block took
+// the monomial-basis slots (mono_put below) and had no use for them.
 // Block partials: a wave's slot sums are added into bpart[slot][wave of the block] in LDS and
 // the block's four waves combined in a fixed order at the end of the launch --
 // partial[slot][block], a quarter of the columns the parameter reduce reads, no global
@@ -91,7 +78,6 @@ struct DevLane {
   int64_t n_rays;
   int64_t wave;
   bool active;
-  double (*zacc)[kBlock];      // __shared__ [kZAcc][kBlock] (kZAcc > 0)
   double (*bpart)[kBlock / 64];  // __shared__ [kBlockSlots][4], zeroed at the kernel start
   double (*mscr)[kMonoStride];   // __shared__ this wave's [8][kMonoStride] transpose rows
 
@@ -124,29 +110,6 @@ struct DevLane {
   __device__ inline double* tape_at(int64_t row) const { return j.tape + row * n_rays + r_ld; }
   __device__ inline int64_t tape_stride() const { return n_rays; }
   __device__ inline int uniform_max(int v) const { return wave_max_i32(v); }
-  // Zernike coefficient contributions of one surface (term j of the surface, slot `slot`):
-  // with kZAcc > 0 the surface's terms j < kZAcc are added per lane in LDS over the hit
-  // point and the replayed Newton iterates and summed over the wave once, at zflush
-  __device__ inline void zemit(int slot, int jt, double v, bool first) {
-    if constexpr (kZAcc > 0) {
-      if (jt < kZAcc) {
-        if (!cst(j.need)[slot]) return;  // uniform
-        if (first)
-          zacc[jt][threadIdx.x] = v;
-        else
-          zacc[jt][threadIdx.x] += v;
-        return;
-      }
-    }
-    emit(slot, v, first);
-  }
-  __device__ inline void zflush(int slot0, int nt) {
-    if constexpr (kZAcc > 0) {
-      const int m = nt < kZAcc ? nt : kZAcc;
-      for (int jt = 0; jt < m; ++jt)
-        if (cst(j.need)[slot0 + jt]) emit(slot0 + jt, zacc[jt][threadIdx.x], true);
-    }
-  }
 };
 
 // RES = false: rays generated from pupil samples (ort_trace_pupil_vjp);
@@ -164,18 +127,11 @@ __global__ __launch_bounds__(kBlock) ORT_ADJ_OCC void adj_kernel(const KArgs a, 
   jm.mono_on = mono_enabled(j);
   if constexpr ((KM & ort::KM_ZERN) != 0) {
     __shared__ double mscr[kBlock / 64][8][kMonoStride];
-    if constexpr (kZAcc > 0) {
-      __shared__ double zacc[kZAcc > 0 ? kZAcc : 1][kBlock];
-      DevLane ln{jm, active ? rid : 0, a.n_rays, rid >> 6, active, zacc, bpart_s,
-                 mscr[threadIdx.x >> 6]};
-      adj_ray<KM, P, RES>(a, jm, ln, rid, active);
-    } else {
-      DevLane ln{jm, active ? rid : 0, a.n_rays, rid >> 6, active, nullptr, bpart_s,
-                 mscr[threadIdx.x >> 6]};
-      adj_ray<KM, P, RES>(a, jm, ln, rid, active);
-    }
+    DevLane ln{jm, active ? rid : 0, a.n_rays, rid >> 6, active, bpart_s,
+               mscr[threadIdx.x >> 6]};
+    adj_ray<KM, P, RES>(a, jm, ln, rid, active);
   } else {
-    DevLane ln{jm, active ? rid : 0, a.n_rays, rid >> 6, active, nullptr, bpart_s, nullptr};
+    DevLane ln{jm, active ? rid : 0, a.n_rays, rid >> 6, active, bpart_s, nullptr};
     adj_ray<KM, P, RES>(a, jm, ln, rid, active);
   }
   __syncthreads();  // the block's waves combined in index order

@@ -46,7 +46,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
                 : closed           ? select_closed(feat)
                                    : select_trace(feat & ~F_AXIAL);
   if (!fn) return ORT_ERR_ARG;
-  const int bs = closed ? closed_block() : kBlock;
+  const int bs = closed ? kClosedBlock : kBlock;
   // F_SPOT: one block per (pair, chunk) of seg_len rays
   int64_t blocks = (feat & F_SPOT) != 0 ? (int64_t)a_in.n_seg * a_in.spot_chunks
                                         : (a_in.n_rays + bs - 1) / bs;
@@ -193,9 +193,10 @@ int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
   // ort_trace_spot: spot pass 1 in the closed-form kernel's epilogue when its blocks can be
   // the spot chunks (one ray per thread, each (field, lambda) segment one pair)
   if (fuse && (feat & F_KM) != 0) return ORT_ERR_ARG;  // no schedule protocol here
-  if (fuse && (feat & (F_KM | F_IA | F_REC | F_WRAY)) == 0 && closed_block() == 256 &&
+  if (fuse && (feat & (F_KM | F_IA | F_REC | F_WRAY)) == 0 &&
       !a.pupil_per_ray && a.n_seg == fuse->pairs && a.n_rays == fuse->pairs * a.seg_len &&
-      fuse->chunks * (int64_t)256 >= a.seg_len && (fuse->chunks - 1) * (int64_t)256 < a.seg_len) {
+      fuse->chunks * (int64_t)kClosedBlock >= a.seg_len &&
+      (fuse->chunks - 1) * (int64_t)kClosedBlock < a.seg_len) {
     a.spot_part1 = fuse->part1;
     a.spot_ops = fuse->ops;
     a.spot_n_ops = fuse->n_ops;

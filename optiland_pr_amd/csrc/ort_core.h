@@ -57,7 +57,7 @@ using ::sin;
 // refinement alone -- the same instructions on the same values, bit-identical to sqrt(x)
 // -- and every other input (0, tiny, inf, NaN, negative) takes the full sequence.
 ORT_INLINE double sqrt(double x) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ORT_NO_FAST_SQRT)
+#if defined(__HIP_DEVICE_COMPILE__)
   // the refinement runs unconditionally (no data-dependent branch around the common
   // case); the rare out-of-range lanes redo it with the full sequence
   const double y = __builtin_amdgcn_rsq(x);
@@ -308,31 +308,12 @@ ORT_INLINE double sdiv(double a, const SharedDiv& d) {
 }
 
 // Quotients that only enter derivatives (the adjoint's reverse sweep and its local jets,
-// whose results are compared at rtol 1e-10, never bit for bit). IEEE by default; the
-// ORT_FAST_RDIV A/B builds take the reciprocal refined twice and one residual step
-// (within an ulp, no scale / fix-up steps) -- measured no faster on the config-5 adjoint
-// (one box, alternating: 268.97 / 261.66 us IEEE vs 273.28 / 267.99 us fast, the fast
-// build's scratch 76 -> 100 B; profiles/r06_ab_rdiv.log).
-ORT_INLINE double rrcp(double b) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ORT_FAST_RDIV)
-  double y = __builtin_amdgcn_rcp(b);
-  double e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-b, y, 1.0);
-  return fma(y, e, y);
-#else
-  return 1.0 / b;
-#endif
-}
-ORT_INLINE double rdiv(double a, double b) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ORT_FAST_RDIV)
-  const double y = rrcp(b);
-  const double q0 = a * y;
-  return fma(fma(-b, q0, a), y, q0);
-#else
-  return a / b;
-#endif
-}
+// whose results are compared at rtol 1e-10, never bit for bit). IEEE: a reciprocal refined
+// twice with one residual step (within an ulp, no scale / fix-up steps) measured no faster
+// on the config-5 adjoint (one box, alternating: 268.97 / 261.66 us IEEE vs 273.28 /
+// 267.99 us, its scratch 76 -> 100 B; profiles/r06_ab_rdiv.log).
+ORT_INLINE double rrcp(double b) { return 1.0 / b; }
+ORT_INLINE double rdiv(double a, double b) { return a / b; }
 
 template <int P>
 struct PlainDiv {
@@ -1239,17 +1220,13 @@ ORT_INLINE T sagnorm_zernike(const T& x, const T& y, const S& R, const S& k, dou
         // there, and its value on the axis is 0). So off that disc the slopes are Gx / Rn,
         // Gy / Rn (2 products instead of a square root and four divisions; < 1e-10
         // relative from the reference's), on it the reference's own chain. The adjoint's
-        // pull-back (ort_sweep.h zern_adj) takes the same branch. (ORT_ZERN_POLAR_CHAIN,
-        // A/B builds: the chain everywhere.)
+        // pull-back (ort_sweep.h zern_adj) takes the same branch.
         const double rho2n = xn * xn + yn * yn;
-#ifndef ORT_ZERN_POLAR_CHAIN
         if (rho2n >= kZernChainRho2) {
           const double inv_rn = 1.0 / Rn;
           dzdx = dzdx + Gx * inv_rn;
           dzdy = dzdy + Gy * inv_rn;
-        } else
-#endif
-        {
+        } else {
           const double rho = sqrt(rho2n);
           double xr, yr, drho_dx, drho_dy, qy, qx;
           div2(x, y, Rn * Rn, xr, yr);
@@ -1511,13 +1488,7 @@ ORT_INLINE void zernike_jet(double x, double y, double R, double k, double Rn, P
     J.zx = J.sx + Fx * iRn;
     J.zy = J.sy + Fy * iRn;
     const double rho2n = xn * xn + yn * yn;
-#ifndef ORT_ZERN_POLAR_CHAIN
-    // (ORT_JET_NO_DISC, A/B builds only: the unguarded derivatives on the disc too)
-#ifdef ORT_JET_NO_DISC
-    if (true) {
-#else
     if (rho2n >= kZernChainRho2) {
-#endif
       J.sx += Gx * iRn;
       J.sy += Gy * iRn;
       const double iRn2 = iRn * iRn;
@@ -1527,7 +1498,6 @@ ORT_INLINE void zernike_jet(double x, double y, double R, double k, double Rn, P
       J.syy += Gyy * iRn2;
       return;
     }
-#endif
     // near the axis the forward's slopes are the reference's eps-guarded chain
     // (sagnorm_zernike): S = Rn sx = a G1 u - c G2 v, T = Rn sy = a G1 v + c G2 u with
     // u, v = xn, yn, a = 1 / (rho (rho + eps)), c = 1 / (rho^2 + eps), G1 = u Gx + v Gy,

@@ -38,33 +38,8 @@
 namespace ort {
 namespace fast {
 
-// Lens constants: from the host table (ort_surface.two_r / one_plus_k / r_sq,
-// ort_surface_optics.u_sq) or recomputed per wave (ORT_NO_HOSTCONST; same values)
-#ifdef ORT_NO_HOSTCONST
-#define ORT_TWO_R(s) (2.0 * (s).radius)
-#define ORT_ONE_PLUS_K(s) (1.0 + (s).conic)
-#define ORT_R_SQ(s) ((s).radius * (s).radius)
-#define ORT_U_SQ(u, u_sq) ((u) * (u))
-#else
-#define ORT_TWO_R(s) ((s).two_r)
-#define ORT_ONE_PLUS_K(s) ((s).one_plus_k)
-#define ORT_R_SQ(s) ((s).r_sq)
-#define ORT_U_SQ(u, u_sq) (u_sq)
-#endif
-
-// ORT_FAST_NOCHECK (timing experiments only, never a shipped build): drop the range
-// checks to measure what they cost
-#ifdef ORT_FAST_NOCHECK
-#define ORT_CHK(bad, cond) ((void)0)
-#define ORT_CHK_UNIFORM(bad, cond) ((void)0)
-#else
 #define ORT_CHK(bad, cond) ::ort::fast::chk((bad), (cond))
 #define ORT_CHK_UNIFORM(bad, cond) ::ort::fast::chk_uniform((bad), (cond))
-#endif
-
-// ORT_SEED_MAG_ONLY (A/B builds, tools/build_variant.py): of round 8's seeded reciprocals
-// the conic normal's magnitude alone -- the generated ray's norm keeps v_rcp -- the build
-// that priced one v_rcp_f64 (profiles/r08_closed_seeds.md)
 
 // The flag a sequence ORs its range failures into (the functions' class B): a per-lane
 // bool, or WaveFlag, the same flags of a whole wave as a mask (bit = lane). A loop that
@@ -327,18 +302,12 @@ ORT_INLINE Ray generate_ray(const ort_segment& s, double px, double py,
   }
   const double z1 = s.epl;
   const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
-#ifndef ORT_SEED_MAG_ONLY
   // the norm's reciprocal seeded by its own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after
   // the step (shared_div_seeded)
   double hm;
   const double mag = sqrt_h(dx * dx + dy * dy + dz * dz, bad, hm);
   ORT_CHK(bad, (mag < 1e-9));  // the (0, 0, 1) branch of ray_generator.py:82-89
   const SharedDiv dm = shared_div_seeded(mag, 2.0 * hm, bad);
-#else
-  const double mag = sqrt(dx * dx + dy * dy + dz * dz, bad);
-  ORT_CHK(bad, (mag < 1e-9));  // the (0, 0, 1) branch of ray_generator.py:82-89
-  const SharedDiv dm = shared_div(mag, bad);
-#endif
   // mag > 0: quot_pos is exact for zero numerators of either sign
   ORT_CHK(bad, !((num_ok(dx) || dx == 0.0) && (num_ok(dy) || dy == 0.0) &&
                  (num_ok(dz) || dz == 0.0)));
@@ -384,11 +353,11 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
   if (k == 0.0) {
     a = r.L * r.L + r.M * r.M + N2;
     b = 2.0 * (r.L * r.x + r.M * r.y - r.N * R + r.N * r.z);
-    c = 0.0 - ORT_TWO_R(s) * r.z + r.x * r.x + r.y * r.y + z2;
+    c = 0.0 - s.two_r * r.z + r.x * r.x + r.y * r.y + z2;
   } else {
     a = k * N2 + r.L * r.L + r.M * r.M + N2;
     b = 2.0 * (k * r.N * r.z + r.L * r.x + r.M * r.y - r.N * R + r.N * r.z);
-    c = k * z2 - ORT_TWO_R(s) * r.z + r.x * r.x + r.y * r.y + z2;
+    c = k * z2 - s.two_r * r.z + r.x * r.x + r.y * r.y + z2;
   }
   const double d = b * b - 4.0 * a * c;
   const double sd = sqrt(d, bad);
@@ -444,11 +413,11 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
   if (k == 0.0) {
     a = r.L * r.L + r.M * r.M + N2;
     S = r.L * r.x + r.M * r.y - r.N * R + r.N * r.z;
-    c = r.x * r.x - ORT_TWO_R(s) * r.z + r.y * r.y + z2;
+    c = r.x * r.x - s.two_r * r.z + r.y * r.y + z2;
   } else {
     a = k * N2 + r.L * r.L + r.M * r.M + N2;
     S = k * r.N * r.z + r.L * r.x + r.M * r.y - r.N * R + r.N * r.z;
-    c = k * z2 - ORT_TWO_R(s) * r.z + r.x * r.x + r.y * r.y + z2;
+    c = k * z2 - s.two_r * r.z + r.x * r.x + r.y * r.y + z2;
   }
   const double SS = S * S, ac = a * c;
   ORT_CHK(bad, !(SS < 0x1p1020 && ::fabs(ac) < 0x1p1020));
@@ -473,9 +442,9 @@ template <class B>
 ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, double& nx,
                                  double& ny, double& nz, B& bad) {
   const double r2 = x * x + y * y;
-  const double a = ORT_ONE_PLUS_K(s) * r2;
+  const double a = s.one_plus_k * r2;
   const double q0 = a * s.inv_r2;
-  const double q = fma(fma(-ORT_R_SQ(s), q0, a), s.inv_r2, q0);
+  const double q = fma(fma(-s.r_sq, q0, a), s.inv_r2, q0);
   const double denom = s.radius * sqrt(1.0 - q, bad);
   const SharedDiv dd = shared_div(denom, bad);
   const double dfdx = sdiv0(x, dd, bad);
@@ -497,9 +466,6 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, doubl
 // product; dot == 0 (sign 0) and NaN take the exact path
 template <class B>
 ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz, B& bad) {
-#ifdef ORT_NO_SIGN_XOR
-  return ::ort::align_normal(r, nx, ny, nz);
-#endif
   const double dot = r.L * nx + r.M * ny + r.N * nz;
   ORT_CHK(bad, !(::fabs(dot) > 0.0));
   const uint64_t sb = (uint64_t)__double_as_longlong(dot) & 0x8000000000000000ull;
@@ -514,7 +480,7 @@ template <class B>
 ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, double u_sq,
                         B& bad) {
   const double dot = align_normal(r, nx, ny, nz, bad);
-  const double root = sqrt(1.0 - ORT_U_SQ(u, u_sq) * (1.0 - dot * dot), bad);
+  const double root = sqrt(1.0 - u_sq * (1.0 - dot * dot), bad);
   const double L0 = r.L, M0 = r.M, N0 = r.N;
   r.L = u * L0 + nx * root - u * nx * dot;
   r.M = u * M0 + ny * root - u * ny * dot;
@@ -533,7 +499,7 @@ ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, doubl
 template <class B>
 ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, B& bad) {
   ORT_CHK(bad, !(::fabs(r.N) > 0.0));
-  const double root = sqrt(1.0 - ORT_U_SQ(u, u_sq) * (1.0 - r.N * r.N), bad);
+  const double root = sqrt(1.0 - u_sq * (1.0 - r.N * r.N), bad);
   const double uN = u * r.N;
   const double sroot = ::copysign(root, r.N);
   r.L = u * r.L + 0.0;
@@ -569,13 +535,9 @@ ORT_INLINE bool lens_range(double R) { return ::fabs(R) <= 0x1p149; }
 // takes the exact path, which forms the reference's expression from the unit normal)
 ORT_INLINE void slope_out(double dfdx, double dfdy, double& nx, double& ny, double& nz,
                           bool& bad) {
-#ifdef ORT_SLOPE_MAXCHK  // (A/B builds) |dfdx|, |dfdy| < 7e13 implies the sum < 9.8e27 + 1
-  // < 1e28: the same guarantee in two compares -- no measurable gain on the MI355X
-  // (profiles/r06_ab_slopemax.log, r06_ab_c3_slope_opk.log)
-  ORT_CHK(bad, !(::fabs(dfdx) < 7e13 && ::fabs(dfdy) < 7e13));
-#else
+  // (two compares, |dfdx|, |dfdy| < 7e13, give the same guarantee: no measurable gain on
+  // the MI355X, profiles/r06_ab_slopemax.log, r06_ab_c3_slope_opk.log)
   ORT_CHK(bad, !(dfdx * dfdx + dfdy * dfdy + 1.0 < 1e28));
-#endif
   nx = dfdx;
   ny = dfdy;
   nz = -1.0;
@@ -603,8 +565,8 @@ ORT_INLINE double sagnorm_even(double x, double y, const ort_surface& s, PD C,
   const double aR = ::fabs(R), sR = R > 0.0 ? 1.0 : -1.0;  // (lens constants)
   ORT_CHK(bad, !lens_range(R));
   const double r2 = x * x + y * y;
-  const double a = ORT_ONE_PLUS_K(s) * r2;  // (1 + k) r2: +-0 at the vertex
-  const SharedDiv rr = shared_div_pos(ORT_R_SQ(s));
+  const double a = s.one_plus_k * r2;  // (1 + k) r2: +-0 at the vertex
+  const SharedDiv rr = shared_div_pos(s.r_sq);
   ORT_CHK(bad, !num_ok0(a));
   const double q = sqrt(1.0 - quot_pos(a, rr), bad);
   const SharedDiv dz = shared_div_pos(aR * (1.0 + q));
@@ -641,8 +603,8 @@ ORT_INLINE double sagnorm_odd(double x, double y, const ort_surface& s, PD C,
   ORT_CHK(bad, !lens_range(R));
   const double r2 = x * x + y * y;
   const double r = sqrt(r2, bad);  // the vertex itself (r2 = 0) takes the exact path
-  const double a = ORT_ONE_PLUS_K(s) * r2;
-  const SharedDiv rr = shared_div_pos(ORT_R_SQ(s));
+  const double a = s.one_plus_k * r2;
+  const SharedDiv rr = shared_div_pos(s.r_sq);
   ORT_CHK(bad, !num_ok0(a));
   const double q = sqrt(1.0 - quot_pos(a, rr), bad);
   const SharedDiv dz = shared_div_pos(aR * (1.0 + q));

@@ -215,8 +215,6 @@ struct HostLane {
   double* tape_at(int64_t row) const { return tp + row; }
   int64_t tape_stride() const { return 1; }
   int uniform_max(int v) const { return v; }
-  void zemit(int slot, int, double v, bool first) { emit(slot, v, first); }
-  void zflush(int, int) {}
   void mono_put(int base, int i, double v) { acc[base + i] += v; }
   void mono_flush(int, int) {}
 };

@@ -43,20 +43,12 @@ void launch_material_nk(const ort_material* mats, const double* coef, int32_t ma
                      mats, coef, mat, w, n, n_out, k_out);
 }
 
-int closed_block() { return kClosedBlock; }
-
 KernelFn select_closed(uint32_t feat) {
-#ifdef ORT_NO_AXIAL  // A/B timing only
-  feat &= ~F_AXIAL;
-#endif
   // the plain form (F_PLAIN): compiled for axial lenses with generated rays, the flagship
   // trace's kernels; every other combination runs the generic form, which is right for
   // any lens
   const uint32_t base = feat & (F_GEN | F_REC | F_MONO | F_WRAY | F_SPOT);
   if ((feat & F_AXIAL) == 0 || (base != F_GEN && base != (F_GEN | F_MONO))) feat &= ~F_PLAIN;
-#ifdef ORT_NO_PLAIN  // A/B timing only
-  feat &= ~F_PLAIN;
-#endif
   switch (feat & (F_GEN | F_REC | F_MONO | F_WRAY | F_AXIAL | F_SPOT | F_PLAIN)) {
     case F_GEN | F_AXIAL | F_PLAIN:
       return trace_closed_kernel<F_GEN | F_AXIAL | F_PLAIN>;

@@ -26,16 +26,13 @@
 
 #include "ort_irradiance.h"
 
-#ifndef ORT_IRR_COMBINE_MIN
-#define ORT_IRR_COMBINE_MIN 16  // same-pixel lanes of a wave worth a cross-lane sum (> 64: never)
-#endif
-
 namespace ortk {
 namespace {
 
 constexpr int kIrrThreads = 1024;      // one workgroup per CU holds a full tile: 16 waves
 constexpr int kIrrSmallThreads = 256;  // finish / VJP
 constexpr int kIrrCombineRounds = 4;   // distinct pixels peeled per wave and contribution
+constexpr int kIrrCombineMin = 16;     // same-pixel lanes of a wave worth a cross-lane sum
 constexpr int64_t kIrrHeader = 64;     // bytes in front of the integer image
 
 struct IrrArgs {
@@ -84,7 +81,7 @@ __device__ inline void irr_add(unsigned long long* dst, int64_t pix, int64_t q, 
     const int64_t lp = __shfl(pix, lead);
     const bool mine = has && pix == lp;
     const unsigned long long m = __ballot(mine);
-    if (__popcll(m) < ORT_IRR_COMBINE_MIN) break;
+    if (__popcll(m) < kIrrCombineMin) break;
     int64_t v = mine ? q : 0;
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
     if (lane == lead && v) atomicAdd(dst + lp, (unsigned long long)v);

@@ -32,11 +32,8 @@ constexpr int64_t kSpotMaxChunks = 256;  // chunks per pair at most: a chunk is 
                                          // times ceil(n_pupil / (256 * 256)) per thread
 // ort_rms_spot (one pair, 1M points in config 5): more, shorter chunks -- 256 blocks of 16
 // points per thread leave the two passes latency-bound; every pass-2 block re-reduces the
-// pass-1 rows (24 B per chunk), so the count stays moderate. ORT_RMS_CHUNKS: A/B builds.
-#ifndef ORT_RMS_CHUNKS
-#define ORT_RMS_CHUNKS 1024
-#endif
-constexpr int64_t kRmsMaxChunks = ORT_RMS_CHUNKS;
+// pass-1 rows (24 B per chunk), so the count stays moderate.
+constexpr int64_t kRmsMaxChunks = 1024;
 
 struct SpotArgs {
   const double* x;
@@ -316,13 +313,9 @@ __global__ __launch_bounds__(kSpotThreads) void rms_spot_vjp_kernel(
   if (i >= n) return;
   const double cx = stats[1], cy = stats[2];
   const double w = *grad_out / (stats[0] * stats[3]);
-#ifndef ORT_TEMPORAL_STORE  // written once, read by the trace's VJP launch (ORT_ST's rule)
-  __builtin_nontemporal_store((x[i] - cx) * w, &gx[i]);
-  __builtin_nontemporal_store((y[i] - cy) * w, &gy[i]);
-#else
-  gx[i] = (x[i] - cx) * w;
-  gy[i] = (y[i] - cy) * w;
-#endif
+  // written once, read by the trace's VJP launch (ORT_ST's rule)
+  ORT_ST(gx[i], (x[i] - cx) * w);
+  ORT_ST(gy[i], (y[i] - cy) * w);
 }
 
 // ort_rms_finish: the taped forward's F_RMS rows -> the rms spot size (ort_reduce.h

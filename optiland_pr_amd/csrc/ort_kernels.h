@@ -39,13 +39,8 @@ namespace ortk {
 // Streaming stores of the ray outputs, records and the adjoint tape (written once, read by
 // a later launch) are issued non-temporal: A/B on the MI355X (rocprofv3 / bench, two
 // repetitions each) DoubleGauss 1M-ray launch 68.7 / 69.0 -> 66.2 / 65.7 us, config 5 step
-// 0.716 / 0.713 -> 0.686 / 0.693 ms (the taped forward). ORT_TEMPORAL_STORE (A/B builds)
-// restores plain stores.
-#ifndef ORT_TEMPORAL_STORE
+// 0.716 / 0.713 -> 0.686 / 0.693 ms (the taped forward) against plain stores.
 #define ORT_ST(lhs, v) __builtin_nontemporal_store((v), &(lhs))
-#else
-#define ORT_ST(lhs, v) ((lhs) = (v))
-#endif
 // the same as the store policy of ort_args.h's store_ray / store_record
 struct StreamStore {
   static __device__ inline __attribute__((always_inline)) void put(double& lhs, double v) {
@@ -57,18 +52,11 @@ struct StreamStore {
 constexpr int kBlock = 256;
 // workgroups of a verify-and-re-trace round of trace_kernel (a multiple of 8, so the
 // grid-stride loop keeps each block on its XCD): 4 per CU, the taped kernel's full
-// occupancy at 4 waves per SIMD. ORT_VERIFY_GRID: A/B builds.
-#ifndef ORT_VERIFY_GRID
-#define ORT_VERIFY_GRID 1024
-#endif
-constexpr int64_t kVerifyGrid = ORT_VERIFY_GRID;
+// occupancy at 4 waves per SIMD.
+constexpr int64_t kVerifyGrid = 1024;
 static_assert(kVerifyGrid % 8 == 0, "XCD-preserving stride");
-// trace_closed_kernel's block size (ort_k_closed.hip; its launch asks closed_block()):
-// a per-TU constant so A/B builds of that TU alone can change it
-#ifndef ORT_CLOSED_BLOCK
-#define ORT_CLOSED_BLOCK 256
-#endif
-constexpr int kClosedBlock = ORT_CLOSED_BLOCK;
+// trace_closed_kernel's block size (ort_k_closed.hip)
+constexpr int kClosedBlock = 256;
 
 // ort_trace_spot -> trace_pupil_impl (ort_api.hip): where the fused spot pass 1 writes;
 // fused reports whether the launch took it
@@ -185,12 +173,11 @@ struct ConvBits {
 // index -- bit j of the AND is set iff no reporting lane missed j, and the max is the
 // last j some reporting lane missed: the same values as the shuffle reductions (six
 // dependent cross-lane steps each, three reductions per Newton surface) at a fraction of
-// the instructions and latency (#ifndef ORT_SHFL_REPORT, A/B builds)
+// the instructions and latency
 __device__ inline void report_newton(const KArgs& a, int si, bool active, int64_t group,
                                      bool group_uniform, ConvBits m, int last_bad, int U = -1,
                                      int j_lo = 0) {
   if (!a.stats) return;
-#ifndef ORT_SHFL_REPORT
   if (group_uniform && a.conv_base == 0) {
     const int Uw = __builtin_amdgcn_readfirstlane(U);
     if (Uw >= 0 && Uw < 128) {
@@ -216,7 +203,6 @@ __device__ inline void report_newton(const KArgs& a, int si, bool active, int64_
       return;
     }
   }
-#endif
   if (!active) {
     m.w0 = m.w1 = ~0ull;
     last_bad = -1;
@@ -376,13 +362,9 @@ __device__ inline __attribute__((always_inline)) double newton_distance(const KA
   // sag + the update's slopes at P(t) (kSlope) and the update; at j = U (the stop test)
   // the same evaluation, the interaction's unit normal formed from those slopes -- for the
   // even / odd / Zernike kinds (n = (dz/dx, dz/dy, -1) / norm, the same operations as their
-  // kNormal evaluation). Kernels with freeform kinds, and ORT_NO_SLOPE A/B builds, evaluate
-  // the unit normal and update with the reference's -n / nz_safe.
-#ifdef ORT_NO_SLOPE
-  constexpr bool kSl = false;
-#else
+  // kNormal evaluation). Kernels with freeform kinds evaluate the unit normal and update
+  // with the reference's -n / nz_safe.
   constexpr bool kSl = ((FEAT & F_KM) & ~(ort::KM_EVEN | ort::KM_ODD | ort::KM_ZERN)) == 0;
-#endif
   for (int j = 0;; ++j) {
     const bool lane_on = active && j <= U;
     if (!__any(lane_on)) break;
@@ -448,16 +430,16 @@ __device__ inline __attribute__((always_inline)) double newton_distance(const KA
 // ~115 VGPRs (4 waves per SIMD); capped at 80 (6 waves, ~128 B scratch per lane) the TMA
 // forward runs 9% faster on the MI355X (334 -> 305 us per 1M-ray launch, rocprofv3; 5
 // waves: 313 us). The even-asphere kernels already fit 6 waves; the rest keep the
-// compiler's choice. ORT_TRACE_WAVES overrides the target for A/B builds.
+// compiler's choice.
 // The taping forward (F_TAPE: up to 11 rows of stores per surface) runs
 // best at 4 waves: TMA 1M rays, taped trace 374 / 328 / 300 us at 6 / 5 / 4 waves per
 // SIMD (rocprofv3 A/B); re-measured with the Cartesian Zernike form (131 VGPRs uncapped),
 // config 5 step 0.750-0.761 / 0.732-0.733 / 0.774-0.775 ms at 3 / 4 / 5 waves.
 // The Newton kernels' deferred-check pass (FAST = true in trace_ray) is compiled for the
 // lenses whose Newton surfaces are even / odd aspheres (the kinds ort_fastpath.h has
-// sequences for) without interactions, per-ray wavelengths or a tape; ORT_NO_NEWTON_FAST
-// (A/B builds) keeps the single exact pass. Measured (config 3, RT-asph 60M rays, rocprofv3
-// PMC + A/B on the MI355X, round 4): every ray stays inside the ranges
+// sequences for) without interactions, per-ray wavelengths or a tape. Measured against the
+// single exact pass (config 3, RT-asph 60M rays, rocprofv3 PMC on the MI355X, round 4):
+// every ray stays inside the ranges
 // (tools/fast_probe.py: 0 re-traced waves), the pass issues 2,598 fp64 VALU instructions
 // per wave instead of 2,725 and 1,611 SALU instead of 2,363 -- but its range tests add as
 // many non-fp64 VALU instructions as the div / sqrt sequences save (4,079 vs 4,060 VALU
@@ -477,12 +459,8 @@ __device__ inline __attribute__((always_inline)) double newton_distance(const KA
 // 7.01-7.02 ms (tools/gpu_r05p.sh, profiles/r05_ab_c3_occupancy.log): 5.
 template <uint32_t FEAT>
 constexpr bool kNewtonFast =
-#ifdef ORT_NO_NEWTON_FAST
-    false;
-#else
     (FEAT & F_KM) != 0 && (FEAT & F_KM & ~(ort::KM_EVEN | ort::KM_ODD)) == 0 &&
     (FEAT & (F_IA | F_WRAY | F_TAPE | F_POL)) == 0;
-#endif
 
 // The verify rounds' grid-stride form (F_STRIDE) usually returns at once and re-traces
 // only after a schedule correction: 2 waves per SIMD, so it carries no scratch (its
@@ -500,11 +478,7 @@ struct TraceWaves {
           ? ((FEAT & F_TAPE) != 0 ? 4 : 6)
           : ((kNewtonFast<FEAT> && (FEAT & F_MONO) != 0) ? 5 : 1);
 };
-#ifdef ORT_TRACE_WAVES
-#define ORT_TRACE_OCC __attribute__((amdgpu_waves_per_eu(ORT_TRACE_WAVES)))
-#else
 #define ORT_TRACE_OCC __attribute__((amdgpu_waves_per_eu(TraceWaves<FEAT>::value)))
-#endif
 // The device side of the host's DeviceLens.verify (raytrace.py) for one workgroup: per
 // (group, Newton surface) the stop rule of newton_raphson.py:140-149 (grid_sag.py:108-140:
 // index >= 1) read from the conv_mask window and last_bad of the launch that ran `sched`.
@@ -593,23 +567,14 @@ __device__ inline void store_tape_point(const KArgs& a, double* tp, const ort::R
 }
 
 // The ray moved to its intersection at distance t: propagate, OPD, aperture clips
-// (standard_surface.py:215-223). AP_PROG = false: without the aperture program (the
-// ORT_NO_AP_PROG A/B builds of the closed-form step)
-template <bool AP_PROG = true>
+// (standard_surface.py:215-223)
 __device__ inline void to_intersection(const KArgs& a, const ort_surface& s, ort::Ray& r,
                                        double t, double alpha, double n_pre) {
   ort::propagate(r, t, alpha);
   ort::add_opd(r, t, n_pre);
   if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-  if constexpr (AP_PROG) {
-    if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-  }
+  if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
 }
-#ifndef ORT_NO_AP_PROG
-constexpr bool kApProg = true;
-#else
-constexpr bool kApProg = false;
-#endif
 
 // One ray through every surface (and the image-space propagate) for trace_kernel.
 // FAST: ort_fastpath.h's sequences with their range failures ORed into `bad` (see
@@ -739,7 +704,7 @@ __device__ inline __attribute__((always_inline)) ort::Ray trace_ray(const KArgs&
       }
     } else {
       // closed-form geometries only: plane / conic normal inline
-      to_intersection<kApProg>(a, s, r, t, alpha, n_pre);
+      to_intersection(a, s, r, t, alpha, n_pre);
       double nx, ny, nz;
       if (s.geometry == ORT_GEOM_PLANE) {
         nx = 0.0; ny = 0.0; nz = 1.0;
@@ -905,7 +870,7 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       }
     } else {
       // closed-form geometries only: plane / conic normal inline
-      to_intersection<kApProg>(a, s, r, t, alpha, n_pre);
+      to_intersection(a, s, r, t, alpha, n_pre);
       double nx, ny, nz;
       if (s.geometry == ORT_GEOM_PLANE) {
         nx = 0.0; ny = 0.0; nz = 1.0;
@@ -1157,28 +1122,17 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
       t = __builtin_nan("");
       geom_bad = true;
     }
-#ifndef ORT_NO_ALPHA_FLAGS
     if constexpr ((FEAT & F_WRAY) != 0)
       ort::propagate(r, t, o.alpha_pre);
     else
       ort::propagate_flagged(r, t, o.alpha_pre, s.flags);
-#else
-    ort::propagate(r, t, o.alpha_pre);
-#endif
     ort::add_opd(r, t, o.n_pre);
     if constexpr (!kPlain) {  // a plain lens has no aperture
       if (s.flags & ORT_SURF_APERTURE) ort::clip_radial(r, s.ap_rmax2, s.ap_rmin2);
-#ifndef ORT_NO_AP_PROG
       if (s.flags & ORT_SURF_APERTURE_PROG) ort::clip_program(r, cst(a.coef) + s.ap_off, s.ap_len);
-#endif
     }
     const bool refl = !kPlain && (s.flags & ORT_SURF_REFLECTIVE) != 0;  // nor a mirror
-#ifndef ORT_NO_FLAT_FAST
-    constexpr bool kFlat = FAST;
-#else
-    constexpr bool kFlat = false;
-#endif
-    if (kFlat && !refl && (is_plane || radius_inf)) {
+    if (FAST && !refl && (is_plane || radius_inf)) {
       ort::fast::refract_flat(r, o.u, o.u_sq, sbad);  // normal (0, 0, +-1): reduced exactly
     } else {
       double nx, ny, nz;
@@ -1274,7 +1228,6 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
       apod_f = ort::apodize(*cst(a.apod), a.px[p], a.py[p]);
     }
   }
-#ifndef ORT_NO_DEFERRED_CHECKS
   ort::fast::WaveFlag fbad{0};  // the fast pass's range failures, one bit per lane
   ort::Ray r = closed_ray_in<FEAT, true>(a, r_ld, lam, wl, fbad);
   closed_surfaces<FEAT, true>(a, r, lam, wl, rid, active, fbad, geom_bad, apod_f);
@@ -1288,11 +1241,6 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
     r = closed_ray_in<FEAT, false>(b, r_ld, lam, wl, bad);
     closed_surfaces<FEAT, false>(b, r, lam, wl, rid, active, bad, geom_bad, apod_f);
   }
-#else
-  const KArgs& b = a;
-  ort::Ray r = closed_ray_in<FEAT, false>(b, r_ld, lam, wl, bad);
-  closed_surfaces<FEAT, false>(b, r, lam, wl, rid, active, bad, geom_bad, apod_f);
-#endif
   if (b.final_mat >= 0) ort::propagate(r, b.final_thickness, final_alpha<FEAT>(b, lam, wl));
   if (geom_bad && b.status && threadIdx.x == 0) atomicOr(b.status, (int)ORT_STATUS_BAD_GEOMETRY);
   if constexpr ((FEAT & F_GEN) != 0) {
@@ -1301,7 +1249,6 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
       atomicOr(b.status, (int)ORT_STATUS_BAD_APODIZATION);
   }
   double inten = ort::intensity(r);
-#ifndef ORT_NO_APOD
   if constexpr ((FEAT & F_GEN) != 0) {
     // Pupil apodization (ray_generator.py:91-95), applied to the stored intensity: the
     // trace only ever multiplies the intensity (absorption) or zeroes it (clipping), so
@@ -1313,7 +1260,6 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
       inten = ort::apodize(*cst(b.apod), b.px[p], b.py[p]) * inten;
     }
   }
-#endif
   if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(b, r, inten, active);
   if (!active) return;
   store_ray<StreamStore>(b, rid, r, &inten);
@@ -1436,7 +1382,6 @@ typedef void (*GeomFn)(const KArgs, const GArgs);
 
 // kernel selection (defined in the ort_k_*.hip translation units)
 KernelFn select_trace(uint32_t feat);      // Newton lenses, any F_GEN / F_REC  (ort_k_trace*.hip)
-int closed_block();                        // its block size                   (ort_k_closed.hip)
 KernelFn select_closed(uint32_t feat);     // closed-form lenses                (ort_k_closed.hip)
 KernelFn select_generate();                // ray generation only               (ort_k_closed.hip)
 KernelFn select_trace_w(uint32_t feat);    // Newton lenses, per-ray wavelengths (ort_k_trace_w.hip)

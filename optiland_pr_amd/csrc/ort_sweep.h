@@ -64,14 +64,6 @@ namespace ortk {
 // propagation distance) goes to lane.emit(slot, v, first); the per-parameter gradient is
 // the sum over rays of its slots weighted by the tangent tables (slot_weight).
 // =====================================================================================
-// The adjoint's tape rows are read once: ORT_NT_LOAD (A/B builds) reads them non-temporal
-// on the device -- measured no gain (config 5 adjoint 428 / 428 vs 436 / 430 us, A/B on the
-// MI355X), so plain loads are the default.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ORT_NT_LOAD)
-#define ORT_TAPE_LD(x) __builtin_nontemporal_load(&(x))
-#else
-#define ORT_TAPE_LD(x) (x)
-#endif
 
 // adjoint of a coordinate-system op: rotations transpose (sin -> -sin), translations
 // are constant offsets (identity on the adjoint)
@@ -175,10 +167,6 @@ ORT_INLINE void zmono_adjoint_deg(Lane& ln, int deg, int slot0, double xn, doubl
 //   double* tape_at(int64_t row)                  this ray's entry of tape row `row`
 //   int64_t tape_stride()                         distance between two tape rows
 //   int    uniform_max(int v)                     max over the rays sharing control flow
-//   void   zemit(int slot, int j, double v, bool first), zflush(int slot0, int nt)
-//                                                 a Zernike term's contribution (term j of
-//                                                 the surface; first: the surface's first);
-//                                                 zflush after the surface's last one
 //   void   mono_put(int slot0, int i, double v), mono_flush(int slot0, int n)
 //                                                 one evaluation's monomial-basis values,
 //                                                 v to slot slot0 + i (zmono_adjoint)
@@ -293,12 +281,6 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
                       double w_sag, double bnx, double bny, double bnz, double nxv,
                       double nyv, double nzv) {
     if constexpr ((KM & ort::KM_ZERN) != 0) {
-#ifdef ORT_ADJ_NO_COEF  // timing builds only (A/B of the coefficient adjoint's cost): one
-      // contribution per call instead of the term pass, so the sweep's data flow stays live
-      if (s.geometry == ORT_GEOM_ZERNIKE && j.zparam)
-        ln.zemit(3 * a.n_surf + s.coef_off, 0, on ? x * w_sag + y * bnx + bny + bnz : 0.0, first);
-      return;
-#endif
       if (s.geometry == ORT_GEOM_ZERNIKE && j.zparam) {
         const double bn = bnx * nxv + bny * nyv + bnz * nzv;
         const double bdx = -nzv * (bnx - nxv * bn);
@@ -312,13 +294,10 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
           // (their adjoint: (bdx, bdy) / Rn), the reference's chain on it
           const double rho2n = xn * xn + yn * yn;
           double ax, ay;
-#ifndef ORT_ZERN_POLAR_CHAIN
           if (rho2n >= ort::kZernChainRho2) {
             ax = bdx * inv_rn;
             ay = bdy * inv_rn;
-          } else
-#endif
-          {
+          } else {
             const double eps = 1e-14;
             const double rho = sqrt(rho2n);
             const double ire = ort::rrcp(rho + eps), iq = ort::rrcp(rho * rho + eps);
@@ -346,8 +325,7 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
         ort::zernike_coef_adjoint(x, y, s.norm_radius, cst(a.zern), s.coef_off, s.n_coef,
                                   cst(a.coef), w_sag, bdx, bdy,
                                   [&](int term, double g) {
-                                    ln.zemit(base + term, term - s.coef_off, on ? g : 0.0,
-                                             first);
+                                    ln.emit(base + term, on ? g : 0.0, first);
                                   });
       }
     }
@@ -502,18 +480,20 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
       const double ci = rc[6 * NR];
       if (ci != 0.0) batt += ci * j.rec[((int64_t)s.rec_slot * 8 + 6) * NR + rid];
     }
+    // the tape rows are read once, with plain loads: non-temporal loads measured no gain
+    // (config 5 adjoint 428 / 428 vs 436 / 430 us on the MI355X)
     const double* tp = ln.tape_at(trow);
     ort::Ray q;
-    q.x = ORT_TAPE_LD(tp[0]);
-    q.y = ORT_TAPE_LD(tp[TS]);
-    q.z = ORT_TAPE_LD(tp[2 * TS]);
-    q.L = ORT_TAPE_LD(tp[3 * TS]);
-    q.M = ORT_TAPE_LD(tp[4 * TS]);
-    q.N = ORT_TAPE_LD(tp[5 * TS]);
+    q.x = tp[0];
+    q.y = tp[TS];
+    q.z = tp[2 * TS];
+    q.L = tp[3 * TS];
+    q.M = tp[4 * TS];
+    q.N = tp[5 * TS];
     q.i = 1.0;
     q.opd = 0.0;
     q.att = 0.0;
-    const double t = ORT_TAPE_LD(tp[6 * TS]);
+    const double t = tp[6 * TS];
     localize(a, s, q);
     const double x1 = q.x + t * q.L;
     const double y1 = q.y + t * q.M;
@@ -603,7 +583,7 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
         // (loaded here, a second round trip per surface; loading the newest iterate with
         // the surface's rows measured the same: config 5 step 0.4917 / 0.4953 vs 0.4925 /
         // 0.4929 ms, tools/gpu_r05u.sh)
-        const double tk = ORT_TAPE_LD(tp[(7 + m) * TS]);
+        const double tk = tp[(7 + m) * TS];
         const double xk = q.x + tk * q.L, yk = q.y + tk * q.M, zk = q.z + tk * q.N;
         D kx, ky, kz;
         const D sk = sagnorm(s, xk, yk, kx, ky, kz);
@@ -651,14 +631,9 @@ ORT_INLINE void adj_ray(const KArgs& a, const AArgs& j, Lane& ln, int64_t rid, b
       // knows of such a schedule (autodiff.vjp_mode), and a schedule only the device saw
       // (a device-verified round raised it) poisons the gradient with NaN instead of
       // truncating it silently
-      const double t0 = U == 0 ? t : ORT_TAPE_LD(tp[(int64_t)(7 + (U <= kHist ? U - 1 : 0)) * TS]);
+      const double t0 = U == 0 ? t : tp[(int64_t)(7 + (U <= kHist ? U - 1 : 0)) * TS];
       closed_adj(s, q, t0, U <= kHist || (s.flags & ORT_SURF_SLOPE_INEXACT) ? tb : 0.0, b, bR,
                  bk);
-    }
-
-    if constexpr ((KM & ort::KM_ZERN) != 0) {
-      if (s.geometry == ORT_GEOM_ZERNIKE && j.zparam && mono_base < 0)
-        ln.zflush(3 * a.n_surf + s.coef_off, s.n_coef);
     }
 
     // localize adjoint: the op list transposed in reverse, then - cs_t
