@@ -12,6 +12,7 @@
 #pragma once
 
 #include "ort_kernels.h"
+#include "ort_reduce.h"  // wave_sum, group8_sum, wave_max_i32, block_sum_lead
 #include "ort_sweep.h"  // adj_ray, vjp_ray (AArgs, JArgs: ort_args.h)
 
 namespace ortk {
@@ -55,22 +56,11 @@ constexpr int kBlockSlots = ORT_VJP_ADJOINT_MAX_SLOTS;
 // Monomial-basis slots (AArgs.n_mono): one evaluation's 2 K values per lane are summed over
 // the wave eight slots at a time through a per-wave LDS transpose -- lane l writes its
 // value for slot row r to scr[r][l]; lane l then adds up row l / 8's entries l % 8,
-// l % 8 + 8, ... (eight of them) and the eight lanes of a row combine by DPP (quad xor 1, 2,
-// row_half_mirror) -- so a chunk of eight slots costs 8 LDS writes, 8 reads and ~16 VALU
+// l % 8 + 8, ... (eight of them) and the eight lanes of a row combine by group8_sum (DPP:
+// quad xor 1, 2, row_half_mirror) -- so a chunk of eight slots costs 8 LDS writes, 8 reads and ~16 VALU
 // per lane instead of eight full wave sums (~20 VALU each). The row stride of 72 doubles
 // puts the eight rows' reads on different LDS banks (2-way at most for 64-bit reads).
 constexpr int kMonoStride = 72;
-
-__device__ inline double group8_sum(double v) {
-  if (__builtin_amdgcn_read_exec() == ~0ull) {
-    v += dpp_step<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_step<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_step<0x141, 0xf>(v);  // row_half_mirror: lane i <- lane 7 - i of its 8
-    return v;
-  }
-  for (int o = 1; o < 8; o <<= 1) v += __shfl_xor(v, o, 64);  // the same sums, same order
-  return v;
-}
 
 struct DevLane {
   const AArgs& j;
@@ -176,15 +166,11 @@ template <int P>
 __global__ __launch_bounds__(kBlock) void vjp_reduce_kernel(const JArgs j, int64_t n_block) {
   const int k = blockIdx.x;
   if (j.p0 + k >= j.n_param) return;  // uniform
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < n_block; b += kBlock) v += j.partial[b * P + k];
-  v = wave_sum(v);
-  __shared__ double ws[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
+  double v[1] = {0.0};
+  for (int64_t b = threadIdx.x; b < n_block; b += kBlock) v[0] += j.partial[b * P + k];
+  const double* ws = block_sum_lead<1, kBlock>(v);
   if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int w = 0; w < kBlock / 64; ++w) s += ws[w];
+    const double s = block_sum_at<1, kBlock>(ws, 0);
     j.grad[j.p0 + k] += s;
   }
 }

@@ -1,5 +1,6 @@
 // ort_k_adj.hip -- adjoint VJP: slot flags, wave-partial reduction, contraction with the
-// tangent tables, and the launch sequence (kernel templates: ort_adjoint.h)
+// tangent tables, and the launch sequence (kernel templates: ort_adjoint.h); the Newton
+// schedule check's launches (newton_decide: ort_kernels.h; the rms rows: ort_reduce.h)
 
 #include "ort_adjoint.h"
 #include "ort_reduce.h"
@@ -29,49 +30,38 @@ __global__ void adj_need_kernel(const AArgs j0, int32_t* need) {
 // and, for the monomial slots, the lens's term matrices (slot_weight / mono_weight).
 __global__ __launch_bounds__(kBlock) void adj_slot_reduce_kernel(const AArgs j) {
   const int slot = blockIdx.x;
-  __shared__ double ws[kBlock / 64];
   if (!cst(j.need)[slot]) {  // uniform: the launch did not sum this slot
     if (threadIdx.x == 0) j.slot_sum[slot] = 0.0;
     return;
   }
   const double* src = j.partial + (int64_t)slot * j.n_wave;
-  double v = 0.0;
+  double v[1] = {0.0};
   int64_t k = threadIdx.x;
   for (; k + 7 * kBlock < j.n_wave; k += 8 * kBlock) {
     double x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) x[u] = src[k + u * kBlock];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v += x[u];
+    for (int u = 0; u < 8; ++u) v[0] += x[u];
   }
-  for (; k < j.n_wave; k += kBlock) v += src[k];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double sum = 0.0;
-    for (int q = 0; q < kBlock / 64; ++q) sum += ws[q];
-    j.slot_sum[slot] = sum;
-  }
+  for (; k < j.n_wave; k += kBlock) v[0] += src[k];
+  const double* ws = block_sum_lead<1, kBlock>(v);
+  if (threadIdx.x == 0) j.slot_sum[slot] = block_sum_at<1, kBlock>(ws, 0);
 }
 
 __global__ __launch_bounds__(kBlock) void adj_grad_kernel(const AArgs j0) {
   const int p = blockIdx.x;
   AArgs j = j0;
   j.mono_on = mono_enabled(j0);
-  __shared__ double ws[kBlock / 64];
-  double v = 0.0;
+  double v[1] = {0.0};
   for (int slot = threadIdx.x; slot < j.n_slot; slot += kBlock) {
     if (!cst(j.need)[slot]) continue;
     const double w = slot_weight(j, slot, p);
-    if (w != 0.0) v += w * j.slot_sum[slot];
+    if (w != 0.0) v[0] += w * j.slot_sum[slot];
   }
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
+  const double* ws = block_sum_lead<1, kBlock>(v);
   if (threadIdx.x == 0) {
-    double g = 0.0;
-    for (int q = 0; q < kBlock / 64; ++q) g += ws[q];
+    const double g = block_sum_at<1, kBlock>(ws, 0);
     if (j.grad_store)
       j.grad[p] = g;
     else

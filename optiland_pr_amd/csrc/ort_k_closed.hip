@@ -1,7 +1,7 @@
 // ort_k_closed.hip -- closed-form-lens kernels and the generation-only kernel
 // (kernel templates: ort_kernels.h; compiled as its own translation unit)
 
-#include "ort_reduce.h"
+#include "ort_kernels.h"
 
 namespace ortk {
 __global__ __launch_bounds__(kBlock) void generate_kernel(const KArgs a) {

@@ -22,7 +22,8 @@
 // Each pass issues its per-ray loads before the reduction of the previous pass's
 // partials, so the two memory round trips overlap.
 
-#include "ort_reduce.h"
+#include "ort_kernels.h"  // image_point_local, SpotFuse / trace_pupil_impl, ORT_ST
+#include "ort_reduce.h"   // block_sum, reduce_rows_n, wave_max, rms_finish_block
 
 namespace ortk {
 namespace {
@@ -56,32 +57,6 @@ struct SpotArgs {
   double* rms_out;      // ort_rms_spot: the rms radius of pair 0 again, as its own scalar
 };
 
-// one image point in the surface frame (visualization/system/utils.py:16-46: the point
-// as a ray with zero direction, localized by the surface's coordinate system)
-__device__ inline void local_point(const SpotArgs& a, int64_t r, double& x, double& y) {
-  ort::Ray p;
-  p.x = a.x[r];
-  p.y = a.y[r];
-  p.z = a.n_ops ? a.z[r] : 0.0;
-  p.L = 0.0; p.M = 0.0; p.N = 0.0;
-  for (int k = 0; k < a.n_ops; ++k) ort::apply_cs_op(p, cst(a.ops)[k]);
-  x = p.x;
-  y = p.y;
-}
-
-// the same for a point already loaded (x, y, z)
-__device__ inline void local_xyz(const SpotArgs& a, double x, double y, double z, double& ox,
-                                 double& oy) {
-  ort::Ray p;
-  p.x = x;
-  p.y = y;
-  p.z = a.n_ops ? z : 0.0;
-  p.L = 0.0; p.M = 0.0; p.N = 0.0;
-  for (int k = 0; k < a.n_ops; ++k) ort::apply_cs_op(p, cst(a.ops)[k]);
-  ox = p.x;
-  oy = p.y;
-}
-
 // A thread's rays j0 + k * 256 (k < per_thread, j < n_pupil) of a chunk, visited in k
 // order, their loads issued four rays at a time ahead of the use (the intensity test no
 // longer gates the coordinate loads): fn(x, y) for each point with i > 0 (every point
@@ -105,22 +80,46 @@ __device__ inline void chunk_points(const SpotArgs& a, int64_t pair, int64_t j0,
     for (int u = 0; u < 4; ++u) {
       if (in[u] && is[u] > 0.0) {  // spot_diagram.py:425-427
         double x, y;
-        local_xyz(a, xs[u], ys[u], zs[u], x, y);
+        image_point_local(a.ops, a.n_ops, xs[u], ys[u], zs[u], x, y);
         fn(x, y);
       }
     }
   }
 }
 
-// sums of the 3 columns of part[0 .. n) (index-strided per thread, then block_sum)
-__device__ inline void reduce_rows(const double* part, int n, double (&v)[3], double* lds) {
-  v[0] = v[1] = v[2] = 0.0;
-  for (int c = threadIdx.x; c < n; c += kSpotThreads) {
-    v[0] += part[c * 3 + 0];
-    v[1] += part[c * 3 + 1];
-    v[2] += part[c * 3 + 2];
+// The pass-2 triple (sum of r^2, max radius, NaN flag). A thread's share of the rows
+// p2[0 .. n), index-strided, in index order:
+__device__ inline void triple_rows(const double* p2, int n, double& t, double& m, double& f) {
+  t = 0.0;
+  m = 0.0;
+  f = 0.0;
+  for (int k = threadIdx.x; k < n; k += kSpotThreads) {
+    t += p2[k * 3 + 0];
+    m = ::fmax(m, p2[k * 3 + 1]);
+    f = ::fmax(f, p2[k * 3 + 2]);
   }
-  block_sum<3>(v, lds);
+}
+// and its block reduction: block_sum for t (every thread gets the total), wave_max for m
+// and f, then thread 0 folds waves 1..3 onto its own wave's value by fmax (only thread 0
+// holds the block's m and f). lds as block_sum<1>'s.
+__device__ inline void triple_block(double& t, double& m, double& f, double* lds) {
+  __shared__ double mx[kSpotThreads / 64][2];
+  double v[1] = {t};
+  block_sum<1>(v, lds);
+  t = v[0];
+  m = wave_max(m);
+  f = wave_max(f);
+  if ((threadIdx.x & 63) == 0) {
+    mx[threadIdx.x >> 6][0] = m;
+    mx[threadIdx.x >> 6][1] = f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kSpotThreads / 64; ++w) {
+      m = ::fmax(m, mx[w][0]);
+      f = ::fmax(f, mx[w][1]);
+    }
+  }
 }
 
 __global__ __launch_bounds__(kSpotThreads) void spot_sum_kernel(const SpotArgs a) {
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(kSpotThreads) void spot_dev_kernel(const SpotArgs a
     if (j < a.n_pupil) {
       const int64_t r = pair * a.n_pupil + j;
       on = !a.i || a.i[r] > 0.0;
-      if (on) local_point(a, r, px, py);
+      if (on) image_point_local(a.ops, a.n_ops, a.x[r], a.y[r], a.n_ops ? a.z[r] : 0.0, px, py);
     }
   }
   // centroid of the field's reference-wavelength spot (spot_diagram.py:317-328)
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(kSpotThreads) void spot_dev_kernel(const SpotArgs a
     c[1] = a.gsum[ref * 3 + 1];
     c[2] = a.gsum[ref * 3 + 2];
   } else {
-    reduce_rows(a.part1 + ref * a.n_chunks * 3, a.n_chunks, c, lds);
+    reduce_rows_n<3>(a.part1 + ref * a.n_chunks * 3, a.n_chunks, c, lds);
   }
   const double cx = c[1] / c[0], cy = c[2] / c[0];
 
@@ -184,23 +183,10 @@ __global__ __launch_bounds__(kSpotThreads) void spot_dev_kernel(const SpotArgs a
   } else {
     chunk_points(a, pair, j0, add);
   }
-  double v[1] = {s};
-  block_sum<1>(v, lds);
-  m = wave_max(m);
-  f = wave_max(f);
-  __shared__ double mx[4][2];
-  if ((threadIdx.x & 63) == 0) {
-    mx[threadIdx.x >> 6][0] = m;
-    mx[threadIdx.x >> 6][1] = f;
-  }
-  __syncthreads();
+  triple_block(s, m, f, lds);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kSpotThreads / 64; ++w) {
-      m = ::fmax(m, mx[w][0]);
-      f = ::fmax(f, mx[w][1]);
-    }
     double* p = a.part2 + (pair * a.n_chunks + blockIdx.x) * 3;
-    p[0] = v[0];
+    p[0] = s;
     p[1] = m;
     p[2] = f;
   }
@@ -210,38 +196,20 @@ __global__ __launch_bounds__(kSpotThreads) void spot_dev_kernel(const SpotArgs a
 __global__ __launch_bounds__(kSpotThreads) void spot_final_kernel(const SpotArgs a) {
   const int64_t pair = blockIdx.x;
   __shared__ double lds[4 * 3];
-  __shared__ double mx[4][2];
   double own[3];
-  const double* p2 = a.part2 + pair * a.n_chunks * 3;
-  double t[1] = {0.0};
-  double m = 0.0, f = 0.0;
+  double t, m, f;
   // pass-2 partials read before pass 1's reduction (overlapping round trips)
-  for (int k = threadIdx.x; k < a.n_chunks; k += kSpotThreads) {
-    t[0] += p2[k * 3 + 0];
-    m = ::fmax(m, p2[k * 3 + 1]);
-    f = ::fmax(f, p2[k * 3 + 2]);
-  }
-  reduce_rows(a.part1 + pair * a.n_chunks * 3, a.n_chunks, own, lds);
-  block_sum<1>(t, lds);
-  m = wave_max(m);
-  f = wave_max(f);
-  if ((threadIdx.x & 63) == 0) {
-    mx[threadIdx.x >> 6][0] = m;
-    mx[threadIdx.x >> 6][1] = f;
-  }
-  __syncthreads();
+  triple_rows(a.part2 + pair * a.n_chunks * 3, a.n_chunks, t, m, f);
+  reduce_rows_n<3>(a.part1 + pair * a.n_chunks * 3, a.n_chunks, own, lds);
+  triple_block(t, m, f, lds);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kSpotThreads / 64; ++w) {
-      m = ::fmax(m, mx[w][0]);
-      f = ::fmax(f, mx[w][1]);
-    }
     const double n = own[0];
     double* o = a.out + pair * 5;
     o[0] = n;
     o[1] = own[1] / n;  // be.mean: sum / count (0 / 0 = NaN)
     o[2] = own[2] / n;
-    o[3] = ::sqrt(t[0] / n);  // be.sqrt(be.mean(x**2 + y**2))
-    o[4] = (f != 0.0 || t[0] != t[0] || n == 0.0) ? __builtin_nan("") : m;  // be.max
+    o[3] = ::sqrt(t / n);  // be.sqrt(be.mean(x**2 + y**2))
+    o[4] = (f != 0.0 || t != t || n == 0.0) ? __builtin_nan("") : m;  // be.max
     if (a.rms_out && pair == 0) *a.rms_out = o[3];
   }
 }
@@ -264,39 +232,21 @@ template <int PASS>
 __global__ __launch_bounds__(kSpotThreads) void spot_pair_kernel(const SpotArgs a) {
   const int64_t pair = blockIdx.x;
   __shared__ double lds[4 * 3];
-  __shared__ double mx[4][2];
   double* o = a.out + pair * 3;
   if constexpr (PASS == 1) {
     double v[3];
-    reduce_rows(a.part1 + pair * a.n_chunks * 3, a.n_chunks, v, lds);
+    reduce_rows_n<3>(a.part1 + pair * a.n_chunks * 3, a.n_chunks, v, lds);
     if (threadIdx.x == 0) {
       o[0] = v[0];
       o[1] = v[1];
       o[2] = v[2];
     }
   } else {
-    const double* p2 = a.part2 + pair * a.n_chunks * 3;
-    double t[1] = {0.0};
-    double m = 0.0, f = 0.0;
-    for (int k = threadIdx.x; k < a.n_chunks; k += kSpotThreads) {
-      t[0] += p2[k * 3 + 0];
-      m = ::fmax(m, p2[k * 3 + 1]);
-      f = ::fmax(f, p2[k * 3 + 2]);
-    }
-    block_sum<1>(t, lds);
-    m = wave_max(m);
-    f = wave_max(f);
-    if ((threadIdx.x & 63) == 0) {
-      mx[threadIdx.x >> 6][0] = m;
-      mx[threadIdx.x >> 6][1] = f;
-    }
-    __syncthreads();
+    double t, m, f;
+    triple_rows(a.part2 + pair * a.n_chunks * 3, a.n_chunks, t, m, f);
+    triple_block(t, m, f, lds);
     if (threadIdx.x == 0) {
-      for (int w = 1; w < kSpotThreads / 64; ++w) {
-        m = ::fmax(m, mx[w][0]);
-        f = ::fmax(f, mx[w][1]);
-      }
-      o[0] = t[0];
+      o[0] = t;
       o[1] = m;
       o[2] = f;
     }

@@ -2,10 +2,10 @@
 // adjoint tape as they trace (F_TAPE, ort_options.tape): the forward of a differentiable
 // trace, whose backward (ort_trace_pupil_vjp with ort_vjp_params.tape) then runs the
 // reverse sweep only. 30 specialisations (kernel templates: ort_kernels.h), plus the
-// single-wavelength ones with the rms spot size's rows in the epilogue (F_RMS, ort_reduce.h)
+// single-wavelength ones with the rms spot size's rows in the epilogue (F_RMS, rms_epilogue)
 // and their verify-round forms (F_STRIDE: a grid of kVerifyGrid workgroups).
 
-#include "ort_reduce.h"
+#include "ort_kernels.h"
 
 namespace ortk {
 

@@ -12,6 +12,7 @@
 // plus per-block partials of the OPD rms over i > 0 and of the tilt fit's weighted sums,
 // reduced in index order by wavefront_final_kernel (deterministic, no atomics).
 
+#include "../../include/optiland_rt.h"  // ort_rays, ort_wavefront_ref
 #include "ort_reduce.h"
 
 namespace ortk {

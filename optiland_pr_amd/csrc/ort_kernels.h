@@ -5,7 +5,8 @@
 // reaches kernels through the select_* functions declared at the end. The argument blocks
 // and every per-ray piece the host library runs too (localize / globalize, interact,
 // pol_step, the geometry predicates, the ray load / store) come from ort_args.h; what is
-// here is the device side: wave operations, the Newton schedule protocol, the kernels.
+// here is the device side: the Newton schedule protocol, the kernels and their reduction
+// epilogues (the wave and block operations themselves: ort_reduce.h).
 //
 // One ray per lane, all surfaces fused in one launch. The ray state
 // (x, y, z, L, M, N, i, opd) stays in VGPRs from the first surface to the image; the
@@ -33,6 +34,7 @@
 #include "ort_fastpath.h"
 #include "ort_interact.h"
 #include "ort_material.h"
+#include "ort_reduce.h"  // wave_sum, wave_max_i32, wave_and_u64, block_sum
 
 namespace ortk {
 
@@ -73,13 +75,6 @@ int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
                      double* rec, ort_newton_stat* newton_stat, int32_t* status, void* stream,
                      SpotFuse* fuse, const ort_polarization* pol = nullptr);
 
-// the F_SPOT epilogue (ort_reduce.h): every thread of the block calls it
-template <uint32_t FEAT>
-__device__ void spot_epilogue(const KArgs& a, const ort::Ray& r, double inten, bool active);
-// the F_RMS epilogue (ort_reduce.h): every thread of the block calls it
-__device__ inline void rms_epilogue(const KArgs& a, const ort::Ray& r, bool active,
-                                    int64_t vb);
-
 // Ray of this thread when every (field, lambda) segment traces the SAME pupil samples
 // (real_ray_tracer.py:74-77 field-major layout: ray = segment * seg_len + p): block b
 // would read pupil chunk b % chunks once per segment, i.e. n_seg times from HBM (the
@@ -102,13 +97,78 @@ __device__ inline int64_t pair_major_ray(const KArgs& a, int64_t vb, int64_t nb)
   return seg * a.seg_len + chunk * kBlock + threadIdx.x;
 }
 
-__device__ inline uint64_t wave_and_u64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v &= __shfl_xor(v, o, 64);
-  return v;
+// One image point (x, y, z) taken into the image surface's frame (visualization/system/
+// utils.py:16-46: the point as a ray with zero direction, localized by the surface's
+// coordinate system; no ops: the point itself, z unused)
+__device__ inline void image_point_local(const ort_cs_op* ops, int n_ops, double x, double y,
+                                         double z, double& ox, double& oy) {
+  ort::Ray p;
+  p.x = x;
+  p.y = y;
+  p.z = n_ops ? z : 0.0;
+  p.L = 0.0; p.M = 0.0; p.N = 0.0;
+  for (int k = 0; k < n_ops; ++k) ort::apply_cs_op(p, cst(ops)[k]);
+  ox = p.x;
+  oy = p.y;
 }
-__device__ inline int wave_max_i32(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
+
+// F_SPOT epilogue of trace_closed_kernel, called by every thread of the block:
+// spot_sum_kernel's pass over one chunk (ort_k_spot.hip, one ray per thread), on the rays
+// still in registers -- the same per-thread values (the point localized by the same ops,
+// masked by i > 0) and the same block_sum, so the partial rows are bit-identical to that
+// kernel's
+template <uint32_t FEAT>
+__device__ void spot_epilogue(const KArgs& a, const ort::Ray& r, double inten, bool active) {
+  static_assert(kClosedBlock == kRedThreads, "one chunk per trace block");
+  double v[3] = {0.0, 0.0, 0.0};
+  if (active && inten > 0.0) {  // spot_diagram.py:425-427
+    double x, y;
+    image_point_local(a.spot_ops, a.spot_n_ops, r.x, r.y, r.z, x, y);
+    v[0] = 1.0;
+    v[1] = 0.0 + x;  // as spot_sum_kernel's 0.0 += x (-0.0 -> +0.0)
+    v[2] = 0.0 + y;
+  }
+  __shared__ double lds[4 * 3];
+  block_sum<3>(v, lds);
+  if (threadIdx.x == 0) {
+    double* o = a.spot_part1 + (int64_t)blockIdx.x * 3;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+  }
+}
+
+// F_RMS epilogue of the taped Newton kernel, called by every thread of the block
+// (RayOperand.rms_spot_size on the traced points, optimization/operand/ray.py:300-340):
+// block vb's row {count, sum x, sum y, sum of (x - mx)^2 + (y - my)^2 about the block's own
+// centroid (mx, my)}, each by block_sum in its fixed order; rms_finish_kernel
+// (ort_k_spot.hip) combines the rows (Chan et al.'s pairwise update: the second moments
+// re-centred on the total centroid), so the rms leaves the forward without a second read of
+// the points
+__device__ inline void rms_epilogue(const KArgs& a, const ort::Ray& r, bool active,
+                                    int64_t vb) {
+  static_assert(kBlock == kRedThreads, "one row per trace workgroup");
+  double v[3] = {0.0, 0.0, 0.0};
+  if (active) {
+    v[0] = 1.0;
+    v[1] = r.x;
+    v[2] = r.y;
+  }
+  __shared__ double lds[4 * 3];
+  block_sum<3>(v, lds);
+  double d[1] = {0.0};
+  if (active) {
+    const double dx = r.x - v[1] / v[0], dy = r.y - v[2] / v[0];
+    d[0] = dx * dx + dy * dy;
+  }
+  block_sum<1>(d, lds);
+  if (threadIdx.x == 0) {
+    double* o = a.rms_part + vb * 4;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+    o[3] = d[0];
+  }
 }
 
 // Same-address atomics from every wave of a large grid serialise in L2, and almost every
@@ -1263,36 +1323,6 @@ __global__ __launch_bounds__(kClosedBlock) __attribute__((amdgpu_waves_per_eu(8)
   if constexpr ((FEAT & F_SPOT) != 0) spot_epilogue<FEAT>(b, r, inten, active);
   if (!active) return;
   store_ray<StreamStore>(b, rid, r, &inten);
-}
-
-// Sum over the 64 lanes of a wave. With the whole wave active: DPP row operations
-// (VALU moves, no LDS round trip per step): quad_perm xor 1 and xor 2, row_half_mirror,
-// row_mirror (a row of 16 summed in every lane), row_bcast15 / row_bcast31 (rows
-// accumulated into lane 63), then lane 63 read into a scalar. Otherwise the xor
-// butterfly through ds_bpermute. Either way a fixed order: deterministic run to run.
-template <int CTRL, int ROW_MASK>
-__device__ inline double dpp_step(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, ROW_MASK, 0xf,
-                                             false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-__device__ inline double wave_sum(double v) {
-  if (__builtin_amdgcn_read_exec() == ~0ull) {
-    v += dpp_step<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_step<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_step<0x141, 0xf>(v);  // row_half_mirror
-    v += dpp_step<0x140, 0xf>(v);  // row_mirror
-    v += dpp_step<0x142, 0xa>(v);  // row_bcast15 -> rows 1, 3
-    v += dpp_step<0x143, 0xc>(v);  // row_bcast31 -> rows 2, 3
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), 63);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-  }
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------

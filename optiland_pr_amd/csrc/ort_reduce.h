@@ -1,28 +1,99 @@
-// ort_reduce.h -- deterministic block reductions for the analysis kernels
-// (ort_k_spot.hip, ort_k_wavefront.hip): wave sums (DPP), then the block's waves
-// in index order, so a reduction over fixed chunks is bit-identical run to run.
+// ort_reduce.h -- every cross-lane and cross-wave step of the kernels, and the one rule of
+// the deterministic sums: lanes by wave_sum, then the block's waves added in index order
+// onto 0.0, so a reduction over fixed chunks is bit-identical run to run. A leaf header: the
+// HIP runtime and nothing of this project.
 #pragma once
 
-#include "ort_kernels.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace ortk {
 
 constexpr int kRedThreads = 256;  // threads per block of the analysis kernels
 
-// wave sums: ort_kernels.h wave_sum (DPP row operations with the whole wave active,
-// the xor butterfly otherwise; a fixed order either way)
-__device__ inline double wave_sum_xor(double v) { return wave_sum(v); }
+// Sum over the 64 lanes of a wave. With the whole wave active: DPP row operations
+// (VALU moves, no LDS round trip per step): quad_perm xor 1 and xor 2, row_half_mirror,
+// row_mirror (a row of 16 summed in every lane), row_bcast15 / row_bcast31 (rows
+// accumulated into lane 63), then lane 63 read into a scalar. Otherwise the xor
+// butterfly through ds_bpermute. Either way a fixed order: deterministic run to run.
+template <int CTRL, int ROW_MASK>
+__device__ inline double dpp_step(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, ROW_MASK, 0xf,
+                                             false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ inline double wave_sum(double v) {
+  if (__builtin_amdgcn_read_exec() == ~0ull) {
+    v += dpp_step<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
+    v += dpp_step<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
+    v += dpp_step<0x141, 0xf>(v);  // row_half_mirror
+    v += dpp_step<0x140, 0xf>(v);  // row_mirror
+    v += dpp_step<0x142, 0xa>(v);  // row_bcast15 -> rows 1, 3
+    v += dpp_step<0x143, 0xc>(v);  // row_bcast31 -> rows 2, 3
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), 63);
+    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+  }
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// every lane gets the sum of its group of eight lanes (wave_sum's first three steps)
+__device__ inline double group8_sum(double v) {
+  if (__builtin_amdgcn_read_exec() == ~0ull) {
+    v += dpp_step<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
+    v += dpp_step<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
+    v += dpp_step<0x141, 0xf>(v);  // row_half_mirror: lane i <- lane 7 - i of its 8
+    return v;
+  }
+  for (int o = 1; o < 8; o <<= 1) v += __shfl_xor(v, o, 64);  // the same sums, same order
+  return v;
+}
 __device__ inline double wave_max(double v) {
   for (int o = 32; o > 0; o >>= 1) v = ::fmax(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ inline int wave_max_i32(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ inline uint64_t wave_and_u64(uint64_t v) {
+  for (int o = 32; o > 0; o >>= 1) v &= __shfl_xor(v, o, 64);
+  return v;
+}
 
-// block-wide sums of NV values (lanes by xor butterfly, then waves 0..NT/64-1 in order);
+// The lead form of the block sum, for a kernel whose totals only one thread (or one per
+// column) needs: the wave sums of NV values, stored by lane 0 of each wave to [wave * NV + k]
+// of the form's own LDS, then one barrier; block_sum_at on the returned rows then gives a
+// thread column k's total. One call per kernel (the rows are not guarded for reuse).
+template <int NV, int NT = kRedThreads>
+__device__ inline const double* block_sum_lead(double (&v)[NV]) {
+  __shared__ double lds[NT / 64 * NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    v[k] = wave_sum(v[k]);
+    if ((threadIdx.x & 63) == 0) lds[(threadIdx.x >> 6) * NV + k] = v[k];
+  }
+  __syncthreads();
+  return lds;
+}
+// waves 0 .. NT / 64 - 1 of column k in index order onto 0.0 (so a -0.0 total comes out +0.0)
+template <int NV, int NT = kRedThreads>
+__device__ inline double block_sum_at(const double* lds, int k) {
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) s += lds[w * NV + k];
+  return s;
+}
+
+// block-wide sums of NV values (lanes by wave_sum, then waves 0..NT/64-1 in order);
 // every thread gets the totals. lds: >= NT / 64 * NV doubles; safe to call back to back.
 template <int NV, int NT = kRedThreads>
 __device__ inline void block_sum(double (&v)[NV], double* lds) {
 #pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum_xor(v[k]);
+  for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0)
@@ -30,11 +101,7 @@ __device__ inline void block_sum(double (&v)[NV], double* lds) {
     for (int k = 0; k < NV; ++k) lds[w * NV + k] = v[k];
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double s = 0.0;
-    for (int ww = 0; ww < NT / 64; ++ww) s += lds[ww * NV + k];
-    v[k] = s;
-  }
+  for (int k = 0; k < NV; ++k) v[k] = block_sum_at<NV, NT>(lds, k);
 }
 
 // column sums of rows part[0 .. n) of NV doubles, each thread striding over rows in
@@ -47,67 +114,6 @@ __device__ inline void reduce_rows_n(const double* part, int n, double (&v)[NV],
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] += part[c * NV + k];
   block_sum<NV>(v, lds);
-}
-
-// F_SPOT epilogue of trace_closed_kernel: spot_sum_kernel's pass over one chunk
-// (ort_k_spot.hip, one ray per thread), on the rays still in registers -- the same
-// per-thread values (the point localized by the same ops, masked by i > 0) and the same
-// block_sum, so the partial rows are bit-identical to that kernel's
-template <uint32_t FEAT>
-__device__ void spot_epilogue(const KArgs& a, const ort::Ray& r, double inten, bool active) {
-  static_assert(kClosedBlock == kRedThreads, "one chunk per trace block");
-  double v[3] = {0.0, 0.0, 0.0};
-  if (active && inten > 0.0) {  // spot_diagram.py:425-427
-    ort::Ray p;
-    p.x = r.x;
-    p.y = r.y;
-    p.z = a.spot_n_ops ? r.z : 0.0;
-    p.L = 0.0; p.M = 0.0; p.N = 0.0;
-    for (int k = 0; k < a.spot_n_ops; ++k) ort::apply_cs_op(p, cst(a.spot_ops)[k]);
-    v[0] = 1.0;
-    v[1] = 0.0 + p.x;  // as spot_sum_kernel's 0.0 += x (-0.0 -> +0.0)
-    v[2] = 0.0 + p.y;
-  }
-  __shared__ double lds[4 * 3];
-  block_sum<3>(v, lds);
-  if (threadIdx.x == 0) {
-    double* o = a.spot_part1 + (int64_t)blockIdx.x * 3;
-    o[0] = v[0];
-    o[1] = v[1];
-    o[2] = v[2];
-  }
-}
-
-// F_RMS epilogue of the taped Newton kernel (RayOperand.rms_spot_size on the traced
-// points, optimization/operand/ray.py:300-340): block vb's row {count, sum x, sum y,
-// sum of (x - mx)^2 + (y - my)^2 about the block's own centroid (mx, my)}, each by
-// block_sum in its fixed order; rms_finish_kernel (ort_k_spot.hip) combines the rows
-// (Chan et al.'s pairwise update: the second moments re-centred on the total centroid),
-// so the rms leaves the forward without a second read of the points
-__device__ inline void rms_epilogue(const KArgs& a, const ort::Ray& r, bool active,
-                                    int64_t vb) {
-  static_assert(kBlock == kRedThreads, "one row per trace workgroup");
-  double v[3] = {0.0, 0.0, 0.0};
-  if (active) {
-    v[0] = 1.0;
-    v[1] = r.x;
-    v[2] = r.y;
-  }
-  __shared__ double lds[4 * 3];
-  block_sum<3>(v, lds);
-  double d[1] = {0.0};
-  if (active) {
-    const double dx = r.x - v[1] / v[0], dy = r.y - v[2] / v[0];
-    d[0] = dx * dx + dy * dy;
-  }
-  block_sum<1>(d, lds);
-  if (threadIdx.x == 0) {
-    double* o = a.rms_part + vb * 4;
-    o[0] = v[0];
-    o[1] = v[1];
-    o[2] = v[2];
-    o[3] = d[0];
-  }
 }
 
 // The rms spot size from the F_RMS rows (ort_rms_finish, and the second workgroup of

@@ -561,7 +561,7 @@ def wavefront_reference(terms, X=None):
 
 # -- the kernels' order of additions, in float64 NumPy -----------------------------------
 def tree64(v):
-    """wave_sum: adjacent lanes pairwise, six times (the DPP steps' tree)."""
+    """wave_sum (csrc/ort_reduce.h): adjacent lanes pairwise, six times (the DPP steps' tree)."""
     for _ in range(6):
         v = v[..., 0::2] + v[..., 1::2]
     return v[..., 0]
@@ -577,7 +577,7 @@ def block_sum(v):
 
 
 def rows_sum(rows):
-    """reduce_rows / reduce_rows_n over [..., n]: thread t adds rows t, t + 256, ... in
+    """reduce_rows_n over [..., n]: thread t adds rows t, t + 256, ... in
     index order, then block_sum."""
     n = rows.shape[-1]
     steps = max(1, -(-n // THREADS))

@@ -1,7 +1,8 @@
 """Shared by tests/test_vjp_sums_cpu.py and tests/test_gpu_vjp_sums.py: the ray sums of the
 gradient kernels (ort_trace_pupil_vjp / ort_trace_sequential_vjp, both modes; adj_kernel's
 emit / mono_put / mono_chunk / group8_sum and block epilogue, adj_slot_reduce_kernel,
-adj_grad_kernel, vjp_kernel / vjp_reduce_kernel<P>; on the host adj_chunks / vjp_chunks)
+adj_grad_kernel, vjp_kernel / vjp_reduce_kernel<P> (their block sums: ort_reduce.h
+block_sum_lead / block_sum_at); on the host adj_chunks / vjp_chunks)
 against an exact sum, at the lane, wave, block and partial-column edges. The maths of the
 per-ray sweep (ort_sweep.h) is pinned elsewhere (adjoint against unrolled, the reference's
 autograd goldens, the oracle's finite differences); here only the summation is.

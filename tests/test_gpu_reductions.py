@@ -241,6 +241,47 @@ def test_rms_finish(gpu, kind, n_rows, variant):
         assert same_bits(rms_finish(gpu, rows)[0][:4], stats[:4])
 
 
+@pytest.fixture(scope="module")
+def newton_lens(gpu):
+    from optiland_pr_amd.raytrace import lens_for
+    from tests._cases import build_lens
+
+    lens = build_lens("rt_asph")  # (alive as long as its lowered form is in use)
+    yield lens_for(lens, [0.5876])
+
+
+def newton_finish_rms(g, dl, rows):
+    """The smallest legal ort_newton_finish_rms call: one round that did not run (flags[0] =
+    0, settled), so the first workgroup checks no statistics and the second finishes the rms."""
+    torch = g.torch
+    ngs = dl.table.n_surfaces  # one group
+    words = torch.zeros(2 * 2 + 1 + 2 * ngs, dtype=torch.int32, device=g.dev)
+    flags, statuses, status_out = words[0:2], words[2:4], words[4:5]
+    sched, copy = words[5:5 + ngs], words[5 + ngs:]
+    nstats = torch.full((2, ngs * 24), 255, dtype=torch.uint8, device=g.dev)
+    stats = torch.empty(5, dtype=torch.float64, device=g.dev)
+    rms = torch.empty((), dtype=torch.float64, device=g.dev)
+    rc = g.lib.ort_newton_finish_rms(C.byref(dl.c), 1, ptr(nstats), 1, 0, ptr(sched), ptr(flags),
+                                     ptr(statuses), ptr(status_out), ptr(copy), ptr(rows),
+                                     rows.shape[0], ptr(stats), ptr(rms), stream(g))
+    g.native.check(rc, "ort_newton_finish_rms")
+    return stats.cpu().numpy(), rms.cpu().numpy()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("n_rows", (1, 255, 256, 257, 4096, 4097))
+def test_rms_finish_same_bits_from_both_entry_points(gpu, newton_lens, kind, n_rows):
+    """ort_rms_finish and the second workgroup of ort_newton_finish_rms run the same
+    rms_finish_block<256, 16>: the same rows give the same bits (4096 rows: the last size
+    held in registers, 4097: the first that re-reads a row)."""
+    rows = up(gpu, R.finish_problem(kind, n_rows, "plain").rows)
+    stats, rms = rms_finish(gpu, rows)
+    stats_n, rms_n = newton_finish_rms(gpu, newton_lens, rows)
+    assert same_bits(stats_n[:4].view(np.uint64), stats[:4].view(np.uint64))
+    assert same_bits(rms_n.view(np.uint64), rms.view(np.uint64))
+    assert math.isnan(stats[4]) and math.isnan(stats_n[4])
+
+
 def test_rms_finish_argument_errors(gpu):
     buf = gpu.torch.zeros(8, dtype=gpu.torch.float64, device=gpu.dev)
     assert gpu.lib.ort_rms_finish(ptr(buf), 0, ptr(buf), ptr(buf), stream(gpu)) == -1

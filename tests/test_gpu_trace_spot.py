@@ -2,7 +2,7 @@
 closed-form kernel's epilogue) against the unfused path on the same inputs -- ort_trace_pupil
 followed by ort_spot_stats. Both the image rays and the statistics must be bit-identical:
 the epilogue forms the same per-thread values and the same block reduction as
-spot_sum_kernel (ort_reduce.h spot_epilogue). The reference side of these numbers is
+spot_sum_kernel (ort_kernels.h spot_epilogue). The reference side of these numbers is
 pinned by test_gpu_spot_stats.py (NumPy statistics, spot_diagram.py:317-357) and
 test_gpu_config_sizes.py (config 1's own workload).
 """
