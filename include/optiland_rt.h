@@ -89,7 +89,12 @@ enum ort_surface_flags {
   /* (v19) the Newton slope is not the sag's derivative: a Zernike surface with a term whose
    * normalisation is not 1 (standard / noll: zernike.py:163-231 omits it from the normal).
    * The adjoint VJP then replays every Newton update, not only the last kHist (4). */
-  ORT_SURF_SLOPE_INEXACT = 1u << 9
+  ORT_SURF_SLOPE_INEXACT = 1u << 9,
+  /* (added without a new version number: 0 stays valid and means "norm_radius holds no
+   * such value") an ORT_GEOM_STANDARD surface with ORT_SURF_INV_R2 whose norm_radius holds
+   * RN(2 / R): the plain closed-form kernels seed the conic normal's 1 / (R sqrt(1 - q))
+   * from it. The results are the same bits with or without the bit. */
+  ORT_SURF_TWO_INV_R = 1u << 10
 };
 
 /* ---- lens-wide frame facts (ort_lens.frame_flags) --------------------------------- */
@@ -160,7 +165,8 @@ typedef struct ort_surface {
   double radius;      /* R (may be +-inf)                                            */
   double conic;       /* k                                                           */
   double tol;         /* Newton tolerance            newton_raphson.py:58-61         */
-  double norm_radius; /* Zernike normalisation radius zernike.py:91-116             */
+  double norm_radius; /* Zernike normalisation radius zernike.py:91-116; with        */
+                      /* ORT_SURF_TWO_INV_R on a standard surface: RN(2 / R)         */
   double ap_rmax2;    /* r_max**2 of a radial aperture  radial.py:50-63              */
   double ap_rmin2;    /* r_min**2                                                    */
   int32_t geometry;   /* enum ort_geometry                                           */

@@ -62,6 +62,7 @@ SURF_INV_R2 = 1 << 6
 SURF_ALPHA_ALL = 1 << 7
 SURF_ALPHA_NONE = 1 << 8
 SURF_SLOPE_INEXACT = 1 << 9  # (v19) the Newton slope is not the sag's derivative
+SURF_TWO_INV_R = 1 << 10  # a standard surface's norm_radius holds RN(2 / R)
 LENS_AXIAL = 1 << 0  # ort_lens.frame_flags
 LENS_PLAIN = 1 << 1  # planes / conics only, no aperture, mirror or record
 

@@ -438,15 +438,34 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
 // standard.py:154-167 with the host's inv_r2 = RN(1 / (R * R)) (ort_core.h
 // normal_conic_rcp: the Markstein-corrected quotient needs no range check of its own --
 // r^2 = 0 / inf / NaN give the reference's 1 - q)
-template <class B>
+// PLAIN (the plain form's kernels): a surface with ORT_SURF_TWO_INV_R carries RN(2 / R) in
+// norm_radius, and 1 / denom, denom = R sqrt(1 - q), is seeded from the root's own h ~
+// 1 / (2 sqrt(1 - q)): y0 = (2 / R) h, then shared_div_seeded's one step and its
+// |denom| <= 2^300 test. The seed's relative error es: 2 h against 1 / g is within
+// 1.5 e0^2 + 2^-51 (sqrt_h, g's rounding included), and three more roundings of 2^-53
+// each follow -- R g, RN(2 / R), the product (2 / R) h -- so for e0 <= 2^-20
+// |es| < 1.5 2^-40 + 2^-51 + 3 2^-53 < 2^-39, and the step leaves es^2 < 2^-78. (|R| in
+// 2^-150 .. 2^150 with the bit, so 2 / R is a normal number and the product rounds as
+// one.) A table without the bit (another producer's) keeps shared_div(denom): a uniform
+// branch on the loaded flags.
+template <bool PLAIN = false, class B>
 ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, double& nx,
                                  double& ny, double& nz, B& bad) {
   const double r2 = x * x + y * y;
   const double a = s.one_plus_k * r2;
   const double q0 = a * s.inv_r2;
   const double q = fma(fma(-s.r_sq, q0, a), s.inv_r2, q0);
-  const double denom = s.radius * sqrt(1.0 - q, bad);
-  const SharedDiv dd = shared_div(denom, bad);
+  double h;
+  const double denom = s.radius * sqrt_h(1.0 - q, bad, h);
+  SharedDiv dd;
+  if constexpr (PLAIN) {
+    if (s.flags & ORT_SURF_TWO_INV_R)
+      dd = shared_div_seeded(denom, s.norm_radius * h, bad);
+    else
+      dd = shared_div(denom, bad);
+  } else {
+    dd = shared_div(denom, bad);
+  }
   const double dfdx = sdiv0(x, dd, bad);
   const double dfdy = sdiv0(y, dd, bad);
   // 1 / mag seeded by 2 h of mag's own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after the step

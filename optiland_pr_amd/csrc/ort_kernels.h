@@ -1079,11 +1079,12 @@ __device__ inline ort::Ray closed_ray_in(const KArgs& a, int64_t r_ld, int& lam,
   return r;
 }
 
-// F_PLAIN: what the fast pass of a plain lens reads of one surface -- 9 of the 44 dwords of
-// ort_surface's record and 4 of the 5 doubles of its optics row (F_MONO; otherwise the row
-// is a per-lane load made where it is used).
+// F_PLAIN: what the fast pass of a plain lens reads of one surface -- 10 fields, 18 of the
+// 44 dwords of ort_surface's record, and 4 of the 5 doubles of its optics row (F_MONO;
+// otherwise the row is a per-lane load made where it is used).
 struct PlainSurf {
   double radius, conic, cs_tz, inv_r2, two_r, one_plus_k, r_sq;
+  double two_inv_r;  // norm_radius: RN(2 / R) with ORT_SURF_TWO_INV_R
   double n_pre, u, alpha_pre, u_sq;
   int32_t geometry, flags;
 };
@@ -1101,6 +1102,7 @@ __device__ inline PlainSurf plain_load(const KArgs& a, int row0, int si) {
   p.two_r = s->two_r;
   p.one_plus_k = s->one_plus_k;
   p.r_sq = s->r_sq;
+  p.two_inv_r = s->norm_radius;
   if constexpr ((FEAT & F_MONO) != 0) {
     const cptr<ort_surface_optics> o = cst(a.optics) + (row0 + si);
     p.n_pre = o->n_pre;
@@ -1122,6 +1124,7 @@ __device__ inline void plain_unpack(const PlainSurf& p, ort_surface& s, ort_surf
   s.two_r = p.two_r;
   s.one_plus_k = p.one_plus_k;
   s.r_sq = p.r_sq;
+  s.norm_radius = p.two_inv_r;
   o.n_pre = p.n_pre;
   o.u = p.u;
   o.alpha_pre = p.alpha_pre;
@@ -1200,7 +1203,7 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
         nx = 0.0; ny = 0.0; nz = 1.0;
       } else if (kPlain || (s.flags & ORT_SURF_INV_R2)) {  // plain: every finite conic has it
         if constexpr (FAST)
-          ort::fast::normal_conic_rcp(r.x, r.y, s, nx, ny, nz, sbad);
+          ort::fast::normal_conic_rcp<kPlain>(r.x, r.y, s, nx, ny, nz, sbad);
         else
           ort::normal_conic_rcp(r.x, r.y, s.radius, s.conic, s.inv_r2, nx, ny, nz);
       } else {

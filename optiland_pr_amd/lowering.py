@@ -253,6 +253,10 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
             if np.isfinite(rr) and 2.0**-300 <= rr <= 2.0**300:
                 row["inv_r2"] = np.float64(1.0) / rr
                 flags |= _abi.SURF_INV_R2
+                # and RN(2 / R) in norm_radius, which no standard surface reads: the seed
+                # factor of the plain closed-form kernel's 1 / (R sqrt(1 - q))
+                row["norm_radius"] = np.float64(2.0) / np.float64(R)
+                flags |= _abi.SURF_TWO_INV_R
         if s.aperture is not None:
             if type(s.aperture) is RadialAperture:  # dedicated radial test
                 flags |= _abi.SURF_APERTURE
