@@ -29,6 +29,13 @@
 // wrongly rounded result) and the divisors' upper bound (a reciprocal small enough to
 // underflow a quotient) stay per operation.
 //
+// The plain form's kernels (F_PLAIN, fast pass only) take three shorter forms where a value
+// is already at hand or a test cannot fire on a finite result: a sphere's norm root
+// sqrt(dfdx^2 + dfdy^2 + 1) seeded from g = sqrt(1 - q) instead of v_rsq (normal_conic_rcp,
+// sqrt_seeded_h), a sphere's 1 / (L^2 + M^2 + N^2) from 2 - a and one step
+// (shared_div_unit), and sqrt(1.0 - v) without its lower-bound test (sqrt_1m). The Newton
+// kernels' calls (template defaults) compile to what they did.
+//
 // Formulas and their order follow ort_core.h (and through it the reference files cited
 // there); only the check placement differs. Host compilation: plain IEEE operations.
 #pragma once
@@ -135,6 +142,48 @@ ORT_INLINE double sqrt_ge1(double x, B& bad) {
   return sqrt_ge1_h(x, bad, h);
 }
 
+// sqrt_ge1_h from a seed y = (1 + es) / sqrt(x) in v_rsq's place, |es| <= e0: the rest of
+// the sequence as it is, so the bounds above hold with es for e0 (the coupled step squares
+// the seed's error whatever produced it: |eh| <= 1.5 es^2 + 2^-51 for the returned h). The
+// caller states where its seed's bound comes from (normal_conic_rcp's sphere branch). A
+// NaN seed gives a NaN root, for state_ok. No test, as sqrt_ge1_h.
+ORT_INLINE double sqrt_seeded_h(double x, double y, double& h_out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double g = x * y;
+  double h = y * 0.5;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  double d = fma(-g, g, x);
+  g = fma(d, h, g);
+  d = fma(-g, g, x);
+  g = fma(d, h, g);
+  h_out = h;
+  return g;
+#else
+  (void)y;
+  h_out = 0.0;
+  return ::sqrt(x);
+#endif
+}
+
+// sqrt(1.0 - v) for the plain form's kernels: sqrt_h without its test. x = fl(1 - v) is
+// <= 0 or >= 2^-53 (v <= 1 - 2^-53 leaves 1 - v >= 2^-53), never in (0, 2^-767) where the
+// test fires on a finite result; x = 0 (rsq = inf, g = 0 inf), x < 0, NaN and +inf
+// (v = -inf) all give NaN, which is sticky in the ray state and caught by state_ok.
+ORT_INLINE double sqrt_1m_h(double x, double& h_out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return sqrt_seeded_h(x, __builtin_amdgcn_rsq(x), h_out);
+#else
+  h_out = 0.0;
+  return ::sqrt(x);
+#endif
+}
+ORT_INLINE double sqrt_1m(double x) {
+  double h;
+  return sqrt_1m_h(x, h);
+}
+
 template <class B>
 ORT_INLINE SharedDiv shared_div(double b, B& bad) {
   SharedDiv d;
@@ -223,6 +272,28 @@ ORT_INLINE SharedDiv shared_div_ge1_seeded(double b, double y0) {
   d.y = fma(y0, e, y0);
 #else
   (void)y0;
+  d.y = 0.0;
+#endif
+  return d;
+}
+
+// 1 / b for b = L^2 + M^2 + N^2 of a unit direction (a sphere's quadratic in the plain
+// form): y0 = 2 - b = (1 - (1 - b)^2) / b, so with |1 - b| <= 2^-27 (tested; false for
+// NaN) the seed's es is within 2^-54 + 2^-53 (2 - b rounds only for b < 1) and
+// shared_div_seeded's one step leaves es^2 < 2^-104. The test stands in for shared_div's
+// |b| <= 2^300 as well.
+template <class B>
+ORT_INLINE SharedDiv shared_div_unit(double b, B& bad) {
+  SharedDiv d;
+  d.b = b;
+  d.ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double y0 = 2.0 - b;
+  const double e = fma(-b, y0, 1.0);
+  d.y = fma(y0, e, y0);
+  ORT_CHK(bad, !(::fabs(1.0 - b) <= 0x1p-27));
+#else
+  (void)bad;
   d.y = 0.0;
 #endif
   return d;
@@ -396,12 +467,15 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
 // The remaining tests are the reference sequence's on the rescaled operands: d' >= 2^-767
 // (d >= 2^-765), |a| <= 2^300 (the divisor range itself; 2 a <= 2^300 was tested before),
 // |-S +- sd'| >= 2^-300.
+// PLAIN, sphere: 1 / a from shared_div_unit (a = |(L, M, N)|^2 ~ 1; its |1 - a| <= 2^-27
+// test replaces |a| <= 2^300). sphere: the caller's k == 0.0, a uniform test made once per
+// surface for this and the normal.
 // k == 0: the reference's c starts (0.0 - 2R z) + x x. 0.0 - p is -p unless p is a zero,
 // where it is +0 and -p may be -0; x x is >= +0 or NaN, and (+-0) + (+0) = +0,
 // (+-0) + w = w: x x - p is the same value.
-template <class B>
+template <bool PLAIN = false, class B>
 ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool radius_inf,
-                                        B& bad) {
+                                        bool sphere, B& bad) {
   if (radius_inf) {
     const double Ns = ::fabs(r.N) > 1e-14 ? r.N : 1e-14;
     return div(-r.z, Ns, bad);
@@ -410,7 +484,7 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
   const double N2 = r.N * r.N;
   const double z2 = r.z * r.z;
   double a, S, c;
-  if (k == 0.0) {
+  if (sphere) {
     a = r.L * r.L + r.M * r.M + N2;
     S = r.L * r.x + r.M * r.y - r.N * R + r.N * r.z;
     c = r.x * r.x - s.two_r * r.z + r.y * r.y + z2;
@@ -423,7 +497,11 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
   ORT_CHK(bad, !(SS < 0x1p1020 && ::fabs(ac) < 0x1p1020));
   const double d = SS - ac;
   const double sd = sqrt(d, bad);
-  const SharedDiv a1 = shared_div(a, bad);
+  SharedDiv a1;
+  if (PLAIN && sphere)
+    a1 = shared_div_unit(a, bad);
+  else
+    a1 = shared_div(a, bad);
   // nonzero numerators (checked): quot_pos and quot agree for either sign of a
   const double n1 = -S + sd, n2 = -S - sd;
   ORT_CHK(bad, !(num_ok(n1) && num_ok(n2)));
@@ -448,18 +526,48 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
 // 2^-150 .. 2^150 with the bit, so 2 / R is a normal number and the product rounds as
 // one.) A table without the bit (another producer's) keeps shared_div(denom): a uniform
 // branch on the loaded flags.
+// PLAIN, sphere (k == 0, the caller's uniform test) on a surface with the bit: the norm's
+// root sqrt(X), X = fl(dfdx^2 + dfdy^2 + 1), takes y = g = RN(sqrt(w)), w = fl(1 - q), in
+// v_rsq(X)'s place (sqrt_seeded_h): g is 1 / sqrt(X) already. With u = 2^-53 and
+// T = (x^2 + y^2) / R^2:
+//   q = T (1 + e1), |e1| <= 4u: r2's two roundings, r_sq = RN(R R), the Markstein quotient;
+//   s = fl(dfdx^2 + dfdy^2) = (T / w)(1 + e2), |e2| <= 8u: g's rounding and R g's, each
+//       squared, the two quotients' (squared), the squares', the sum's;
+//   so s = (q / w)(1 + e3), |e3| <= 12.2u, and X = (1 + s)(1 + rho), |rho| <= u;
+//   w = 1 - q + eta, |eta| <= u / 2 (w in [1/2, 1]; below 1/2 the difference is exact).
+// X w = (w + q (1 + e3))(1 + rho) = (1 + eta + q e3)(1 + rho), q <= 1: |X w - 1| < 13.8u.
+// The errors are absolute, against 1: a small w does not amplify them. g^2 = w (1 + 2 gam),
+// |gam| <= u, so |g sqrt(X) - 1| < 6.9u + u + O(u^2) < 2^-50, whatever the hit height, where
+// v_rsq has e0 = 2^-20: the sequence's bounds hold with room (sqrt_seeded_h).
+//   q = 0 (vertex): w = 1, g = 1, dfdx = dfdy = +-0, X = 1: the seed is exact.
+//   w at its low end: 2^-53, the least positive fl(1 - q) (sqrt_1m_h); s <= 2^54 then, and
+//     no product above under- or overflows (|x|, |y| >= 2^-300 or +0, checked by sdiv0).
+//   w <= 0: g is NaN, and so are denom, the slopes, X and the normal: state_ok.
+// Nothing but the seed changes: mag is the same RN(sqrt(X)) and 2 hm seeds 1 / mag as
+// before. (Dropping the coupled step as well -- gm = X g, hm = g / 2 into the two
+// corrections -- is not done: the last correction rounds g + d h, which is sqrt(X) off by
+// (ulp / 2) |eh|, and lands on the right side of a rounding boundary that sqrt(X) comes
+// within 2^-107 of (X = 1 + 2^-52 is one) only because the coupled step leaves h at its
+// own rounding, |eh| ~ 2^-53; g / 2 has 2^-50.) k != 0 and tables without the bit keep
+// v_rsq(X).
 template <bool PLAIN = false, class B>
-ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, double& nx,
-                                 double& ny, double& nz, B& bad) {
+ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, bool sphere,
+                                 double& nx, double& ny, double& nz, B& bad) {
   const double r2 = x * x + y * y;
   const double a = s.one_plus_k * r2;
   const double q0 = a * s.inv_r2;
   const double q = fma(fma(-s.r_sq, q0, a), s.inv_r2, q0);
-  double h;
-  const double denom = s.radius * sqrt_h(1.0 - q, bad, h);
+  double h, g;
+  if constexpr (PLAIN)
+    g = sqrt_1m_h(1.0 - q, h);
+  else
+    g = sqrt_h(1.0 - q, bad, h);
+  const double denom = s.radius * g;
   SharedDiv dd;
+  bool seeded = false;  // the surface carries the bit
   if constexpr (PLAIN) {
-    if (s.flags & ORT_SURF_TWO_INV_R)
+    seeded = (s.flags & ORT_SURF_TWO_INV_R) != 0;
+    if (seeded)
       dd = shared_div_seeded(denom, s.norm_radius * h, bad);
     else
       dd = shared_div(denom, bad);
@@ -468,9 +576,13 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, doubl
   }
   const double dfdx = sdiv0(x, dd, bad);
   const double dfdy = sdiv0(y, dd, bad);
+  double hm, mag;
+  const double X = dfdx * dfdx + dfdy * dfdy + 1.0;
+  if (PLAIN && seeded && sphere)
+    mag = sqrt_seeded_h(X, g, hm);
+  else
+    mag = sqrt_ge1_h(X, bad, hm);
   // 1 / mag seeded by 2 h of mag's own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after the step
-  double hm;
-  const double mag = sqrt_ge1_h(dfdx * dfdx + dfdy * dfdy + 1.0, bad, hm);
   const SharedDiv dm = shared_div_ge1_seeded(mag, 2.0 * hm);
   // dfdx = x / denom with x checked (|x| in [2^-300, 2^300] or +0) and |denom| <= 2^300:
   // |dfdx| >= 2^-600 or +-0, and |dfdx| <= mag -- in range for the positive divisor
@@ -478,6 +590,13 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, doubl
   nx = quot_pos(dfdx, dm);
   ny = quot_pos(dfdy, dm);
   nz = quot(-1.0, dm);  // constant numerator: always in range
+}
+
+// the Newton kernels' call: no sphere branch outside the plain form
+template <class B>
+ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, double& nx,
+                                 double& ny, double& nz, B& bad) {
+  normal_conic_rcp<false>(x, y, s, false, nx, ny, nz, bad);
 }
 
 // rays/real_rays.py:511-547 (ort_core.h align_normal) for dot != 0: sign(dot) is +-1 and
@@ -495,11 +614,16 @@ ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz,
 }
 
 // rays/real_rays.py:141-163 (ort_core.h refract); u_sq = RN(u * u) from the host table
-template <class B>
+template <bool PLAIN = false, class B>
 ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, double u_sq,
                         B& bad) {
   const double dot = align_normal(r, nx, ny, nz, bad);
-  const double root = sqrt(1.0 - u_sq * (1.0 - dot * dot), bad);
+  const double v = u_sq * (1.0 - dot * dot);
+  double root;
+  if constexpr (PLAIN)
+    root = sqrt_1m(1.0 - v);
+  else
+    root = sqrt(1.0 - v, bad);
   const double L0 = r.L, M0 = r.M, N0 = r.N;
   r.L = u * L0 + nx * root - u * nx * dot;
   r.M = u * M0 + ny * root - u * ny * dot;
@@ -515,10 +639,15 @@ ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, doubl
 //   N' = (u N + sign(N) root) - (u sign(N)) |N| = (u N + sign(N) root) - u N.
 // N == 0 / NaN takes the exact path; a non-finite L or M only reaches here on a ray that
 // already failed a check (or came in non-finite, which closed_ray_in flags).
-template <class B>
+template <bool PLAIN = false, class B>
 ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, B& bad) {
   ORT_CHK(bad, !(::fabs(r.N) > 0.0));
-  const double root = sqrt(1.0 - u_sq * (1.0 - r.N * r.N), bad);
+  const double v = u_sq * (1.0 - r.N * r.N);
+  double root;
+  if constexpr (PLAIN)
+    root = sqrt_1m(1.0 - v);
+  else
+    root = sqrt(1.0 - v, bad);
   const double uN = u * r.N;
   const double sroot = ::copysign(root, r.N);
   r.L = u * r.L + 0.0;

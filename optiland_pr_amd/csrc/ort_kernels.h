@@ -1170,9 +1170,10 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     // register and back at every surface.
     bool sbad = false;
     double t;
+    const bool sphere = s.conic == 0.0;  // uniform: the quadratic's and the normal's branch
     if constexpr (FAST) {
       t = is_plane ? ort::fast::distance_plane(r, sbad)
-                   : ort::fast::distance_conic_folded(r, s, radius_inf, sbad);
+                   : ort::fast::distance_conic_folded<kPlain>(r, s, radius_inf, sphere, sbad);
     } else {
       t = is_plane ? ort::distance_plane(r) : ort::distance_conic(r, s.radius, s.conic, radius_inf);
     }
@@ -1196,14 +1197,14 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     }
     const bool refl = !kPlain && (s.flags & ORT_SURF_REFLECTIVE) != 0;  // nor a mirror
     if (FAST && !refl && (is_plane || radius_inf)) {
-      ort::fast::refract_flat(r, o.u, o.u_sq, sbad);  // normal (0, 0, +-1): reduced exactly
+      ort::fast::refract_flat<kPlain>(r, o.u, o.u_sq, sbad);  // normal (0, 0, +-1): reduced exactly
     } else {
       double nx, ny, nz;
       if (is_plane) {
         nx = 0.0; ny = 0.0; nz = 1.0;
       } else if (kPlain || (s.flags & ORT_SURF_INV_R2)) {  // plain: every finite conic has it
         if constexpr (FAST)
-          ort::fast::normal_conic_rcp<kPlain>(r.x, r.y, s, nx, ny, nz, sbad);
+          ort::fast::normal_conic_rcp<kPlain>(r.x, r.y, s, sphere, nx, ny, nz, sbad);
         else
           ort::normal_conic_rcp(r.x, r.y, s.radius, s.conic, s.inv_r2, nx, ny, nz);
       } else {
@@ -1213,7 +1214,7 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
         ort::reflect(r, nx, ny, nz);
       } else {
         if constexpr (FAST)
-          ort::fast::refract(r, nx, ny, nz, o.u, o.u_sq, sbad);
+          ort::fast::refract<kPlain>(r, nx, ny, nz, o.u, o.u_sq, sbad);
         else
           ort::refract(r, nx, ny, nz, o.u);
       }
