@@ -125,6 +125,22 @@ int ort_host_trace_sequential_polarized(const ort_lens* lens, const ort_rays* ra
 int ort_host_generate_rays(const double* px, const double* py, ort_rays* rays_out,
                            const ort_batch* batch);
 
+/* ort_trace_pupil_scatter / ort_trace_sequential_scatter / ort_bsdf_scatter on host memory
+ * (added within v3): the kernels' scatter step (csrc/ort_scatter.h) inside the host trace.
+ * scat->bsdf is a host pointer; same argument checks as the device entry points. */
+int ort_host_trace_pupil_scatter(const ort_lens* lens, const double* px, const double* py,
+                                 ort_rays* rays_out, const ort_batch* batch,
+                                 const ort_options* opt, double* rec, int32_t* updates,
+                                 int32_t* status, const ort_scatter* scat);
+int ort_host_trace_sequential_scatter(const ort_lens* lens, const ort_rays* rays_in,
+                                      ort_rays* rays_out, const ort_batch* batch,
+                                      const ort_options* opt, double* rec, int32_t* updates,
+                                      int32_t* status, const ort_scatter* scat);
+int ort_host_bsdf_scatter(const double* L, const double* M, const double* N, const double* nx,
+                          const double* ny, const double* nz, int64_t n, int32_t surface_index,
+                          const ort_bsdf* bsdf, const ort_scatter* scat, double* out_L,
+                          double* out_M, double* out_N, int32_t* status);
+
 /* threads used by the calls (OpenMP; <= 0: the OpenMP default) */
 void ort_host_set_threads(int32_t n);
 

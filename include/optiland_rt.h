@@ -489,8 +489,11 @@ enum ort_status {
   ORT_STATUS_CHEBYSHEV_RANGE = 1u << 1, /* chebyshev.py:203-215 ValueError          */
   ORT_STATUS_BAD_GEOMETRY = 1u << 2,    /* a surface with an unknown geometry id: its
                                            rays are NaN (never a silent substitute)  */
-  ORT_STATUS_BAD_APODIZATION = 1u << 3  /* ort_batch.apod holds an unknown kind: the
+  ORT_STATUS_BAD_APODIZATION = 1u << 3, /* ort_batch.apod holds an unknown kind: the
                                            generated intensities are NaN             */
+  ORT_STATUS_SCATTER_ATTEMPTS = 1u << 4 /* a BSDF's rejection loop used up
+                                           ort_scatter.max_attempts draws: that ray's
+                                           direction is NaN                          */
 };
 
 /* Pupil distribution generated on the device (distribution.py:72-408), see
@@ -1041,6 +1044,64 @@ int ort_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in
                                    const ort_options* opt, double* rec,
                                    ort_newton_stat* newton_stat, int32_t* status,
                                    const ort_polarization* pol, void* stream);
+
+/* BSDF surface scattering (scatter.py:23-111, applied by interactions/base.py:111-128 after
+ * the refraction / reflection; added within v21: new structs and entry points only).
+ *
+ * At a surface whose ort_bsdf.kind is not NONE the direction after the interaction is
+ * replaced, in the surface's local frame, by the reference's scatter(): a point (x, y) of
+ * the unit disk (LAMBERTIAN: (sqrt(u1) cos t, sqrt(u1) sin t); GAUSSIAN: sigma sqrt(-2 ln u1)
+ * (cos t, sin t); t = 2 pi u2) is added to the ray's components in the tangent frame
+ * (a, b) of the geometry's raw normal n, and the draw is repeated while 1 - sx^2 - sy^2 < 0.
+ * The reference draws from a global generator; here the two uniforms of every (ray,
+ * surface, attempt) are one Philox4x32-10 block with
+ *   key      (seed & 0xffffffff, seed >> 32)
+ *   counter  (ray & 0xffffffff, ray >> 32, surface_index, attempt),  ray = the ray's index
+ *            in the batch + ray_offset, surface_index = its index in lens.surfaces
+ *   u1 = (((o0 >> 5) << 26 | (o1 >> 6)) + 1) 2^-53, u2 likewise from o2, o3 (in (0, 1])
+ * so the same seed gives the same rays under any launch shape, any split of a batch
+ * (ray_offset) and a verify round's re-trace. After max_attempts rejected draws the
+ * direction is NaN and ORT_STATUS_SCATTER_ATTEMPTS is set. */
+enum ort_bsdf_kind { ORT_BSDF_NONE = 0, ORT_BSDF_LAMBERTIAN = 1, ORT_BSDF_GAUSSIAN = 2 };
+typedef struct ort_bsdf { /* one per traced surface */
+  int32_t kind;           /* ort_bsdf_kind */
+  int32_t reserved;
+  double sigma;           /* GAUSSIAN */
+} ort_bsdf; /* 16 bytes */
+typedef struct ort_scatter {
+  uint64_t seed;
+  int64_t ray_offset;     /* added to the ray's index in the batch (>= 0) */
+  int32_t max_attempts;   /* >= 1 */
+  int32_t reserved;
+  const ort_bsdf* bsdf;   /* device, [n_surfaces] (ort_bsdf_scatter: unused, may be NULL) */
+} ort_scatter; /* 32 bytes */
+
+/* ort_trace_pupil / ort_trace_sequential with scattering surfaces: the same arguments plus
+ * `scat` (required, with scat->bsdf). The rays are traced by the trace_kernel<F_SCAT>
+ * family (every Newton kind compiled in, never the closed-form fast pass) through the same
+ * schedule / verify protocol. Surfaces of kind NONE, and so every ray of an all-NONE table,
+ * are the plain trace's operation for operation.
+ * ORT_ERR_ARG: per-ray wavelengths (batch->w), a tape or rms request, max_attempts < 1,
+ * ray_offset < 0, lenses with thin-lens, phase, grating or NURBS surfaces. The VJP entry
+ * points take no ort_scatter: a scattered trace has no derivative here. */
+int ort_trace_pupil_scatter(const ort_lens* lens, const double* px, const double* py,
+                            ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
+                            double* rec, ort_newton_stat* newton_stat, int32_t* status,
+                            const ort_scatter* scat, void* stream);
+int ort_trace_sequential_scatter(const ort_lens* lens, const ort_rays* rays_in,
+                                 ort_rays* rays_out, const ort_batch* batch,
+                                 const ort_options* opt, double* rec,
+                                 ort_newton_stat* newton_stat, int32_t* status,
+                                 const ort_scatter* scat, void* stream);
+/* BaseBSDF.scatter(rays, nx, ny, nz) (scatter.py:158-194) for n directions and normals on
+ * the device, one ray per lane: out = the scattered directions (may alias the inputs).
+ * Ray r draws as ray r + scat->ray_offset at surface_index. bsdf: one record in host memory
+ * (LAMBERTIAN or GAUSSIAN), passed to the kernel by value. status (nullable, device int32)
+ * is initialised by this call. */
+int ort_bsdf_scatter(const double* L, const double* M, const double* N, const double* nx,
+                     const double* ny, const double* nz, int64_t n, int32_t surface_index,
+                     const ort_bsdf* bsdf, const ort_scatter* scat, double* out_L,
+                     double* out_M, double* out_N, int32_t* status, void* stream);
 
 /* Error codes */
 enum ort_error {

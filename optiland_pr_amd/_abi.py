@@ -104,6 +104,7 @@ STATUS_ZERNIKE_RANGE = 1 << 0
 STATUS_CHEBYSHEV_RANGE = 1 << 1
 STATUS_BAD_GEOMETRY = 1 << 2
 STATUS_BAD_APODIZATION = 1 << 3
+STATUS_SCATTER_ATTEMPTS = 1 << 4
 
 CS_OP = np.dtype(
     [("kind", "<i4"), ("reserved", "<i4"), ("p", "<f8", (3,))], align=True
@@ -212,6 +213,13 @@ POL_IGNORE = 0
 POL_MATRICES = 1
 POL_POLARIZED = 2
 POL_UNPOLARIZED = 3
+
+# enum ort_bsdf_kind / struct ort_bsdf (one per traced surface; ort_scatter)
+BSDF_NONE = 0
+BSDF_LAMBERTIAN = 1
+BSDF_GAUSSIAN = 2
+BSDF = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("sigma", "<f8")], align=True)
+assert BSDF.itemsize == 16
 
 # enum ort_material_kind
 MAT_IDEAL = 0

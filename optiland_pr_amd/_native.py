@@ -143,6 +143,16 @@ class ort_polarization(C.Structure):  # added within v21 (ort_trace_*_polarized)
     ]
 
 
+class ort_scatter(C.Structure):  # added within v21 (ort_trace_*_scatter, ort_bsdf_scatter)
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("ray_offset", C.c_int64),
+        ("max_attempts", C.c_int32),
+        ("reserved", C.c_int32),
+        ("bsdf", C.c_void_p),
+    ]
+
+
 class ort_spot_layout(C.Structure):
     _fields_ = [
         ("n_pupil", C.c_int64),
@@ -165,6 +175,7 @@ class ort_wavefront_ref(C.Structure):
 PTR, I32, I64, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 LENS, RAYS, BATCH, OPTIONS = (C.POINTER(s) for s in (ort_lens, ort_rays, ort_batch, ort_options))
 VJP, POL, SPOT = (C.POINTER(s) for s in (ort_vjp_params, ort_polarization, ort_spot_layout))
+SCAT = C.POINTER(ort_scatter)
 
 DEVICE_PROTOTYPES = {
     "ort_abi_version": (C.c_int, []),
@@ -212,6 +223,12 @@ DEVICE_PROTOTYPES = {
                                             POL, PTR]),
     "ort_trace_sequential_polarized": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR, PTR,
                                                  POL, PTR]),
+    "ort_trace_pupil_scatter": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR, PTR,
+                                          SCAT, PTR]),
+    "ort_trace_sequential_scatter": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR, PTR,
+                                               SCAT, PTR]),
+    "ort_bsdf_scatter": (C.c_int, [PTR, PTR, PTR, PTR, PTR, PTR, I64, I32, PTR, SCAT, PTR, PTR,
+                                   PTR, PTR, PTR]),
 }
 
 HOST_PROTOTYPES = {
@@ -235,6 +252,12 @@ HOST_PROTOTYPES = {
     "ort_host_trace_sequential_polarized": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR,
                                                       PTR, PTR, POL]),
     "ort_host_generate_rays": (C.c_int, [PTR, PTR, RAYS, BATCH]),
+    "ort_host_trace_pupil_scatter": (C.c_int, [LENS, PTR, PTR, RAYS, BATCH, OPTIONS, PTR, PTR,
+                                               PTR, SCAT]),
+    "ort_host_trace_sequential_scatter": (C.c_int, [LENS, RAYS, RAYS, BATCH, OPTIONS, PTR, PTR,
+                                                    PTR, SCAT]),
+    "ort_host_bsdf_scatter": (C.c_int, [PTR, PTR, PTR, PTR, PTR, PTR, I64, I32, PTR, SCAT, PTR,
+                                        PTR, PTR, PTR]),
 }
 
 EXPORTS = tuple(DEVICE_PROTOTYPES)

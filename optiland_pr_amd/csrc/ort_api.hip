@@ -39,9 +39,13 @@ int launch_geom(const ort_lens* lens, int32_t surface, int64_t n, const ort_rays
 
 int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
   if (a_in.n_rays == 0) return ORT_OK;
-  const bool pol = (feat & F_POL) != 0;  // coated / polarized: always its own family
-  const bool closed = !pol && (feat & F_IA) == 0 && (feat & F_KM) == 0;
-  KernelFn fn = pol                ? select_trace_pol(feat)
+  // coated / polarized, or scattering: always its own family
+  const bool scat = (feat & F_SCAT) != 0;
+  const bool pol = (feat & F_POL) != 0;
+  const bool own_family = pol || scat;
+  const bool closed = !own_family && (feat & F_IA) == 0 && (feat & F_KM) == 0;
+  KernelFn fn = scat               ? select_trace_scat(feat)
+                : pol              ? select_trace_pol(feat)
                 : (feat & F_IA) != 0 ? select_trace_ia(feat & ~F_AXIAL)
                 : closed           ? select_closed(feat)
                                    : select_trace(feat & ~F_AXIAL);
@@ -52,7 +56,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
                                         : (a_in.n_rays + bs - 1) / bs;
   // a verify-and-re-trace round (statistics to check, or a run_if flag) of a kernel with a
   // grid-stride form (F_STRIDE): at most kVerifyGrid workgroups
-  if (!closed && !pol && (feat & F_IA) == 0 && (a_in.vstats || a_in.run_if) && blocks > kVerifyGrid) {
+  if (!closed && !own_family && (feat & F_IA) == 0 && (a_in.vstats || a_in.run_if) && blocks > kVerifyGrid) {
     if (KernelFn fs = select_trace((feat | F_STRIDE) & ~F_AXIAL)) {
       fn = fs;
       blocks = kVerifyGrid;
@@ -62,7 +66,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
   KArgs a = a_in;
   // Newton kernels on generated rays whose segments share one pupil: chunk-major block
   // order (pair_major_ray), where it is a bijection over whole blocks
-  a.block_remap = !pol && (feat & F_KM) != 0 && (feat & F_IA) == 0 && (feat & F_GEN) != 0 &&
+  a.block_remap = !own_family && (feat & F_KM) != 0 && (feat & F_IA) == 0 && (feat & F_GEN) != 0 &&
                   !a.pupil_per_ray && a.seg && a.n_seg > 1 && a.seg_len % kBlock == 0 &&
                   a.n_rays == (int64_t)a.n_seg * a.seg_len;
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(bs), 0, stream, a);
@@ -156,6 +160,52 @@ int ort_trace_sequential_polarized(const ort_lens* lens, const ort_rays* rays_in
   return launch(a, feat, s);
 }
 
+int ort_trace_pupil_scatter(const ort_lens* lens, const double* px, const double* py,
+                            ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
+                            double* rec, ort_newton_stat* newton_stat, int32_t* status,
+                            const ort_scatter* scat, void* stream) {
+  if (!scat) return ORT_ERR_ARG;
+  return trace_pupil_impl(lens, px, py, rays_out, batch, opt, rec, newton_stat, status, stream,
+                          nullptr, nullptr, scat);
+}
+
+int ort_trace_sequential_scatter(const ort_lens* lens, const ort_rays* rays_in,
+                                 ort_rays* rays_out, const ort_batch* batch,
+                                 const ort_options* opt, double* rec,
+                                 ort_newton_stat* newton_stat, int32_t* status,
+                                 const ort_scatter* scat, void* stream) {
+  if (!rays_in || !rays_out || !batch || !scat) return ORT_ERR_ARG;
+  if (batch->n_rays == 0) return ORT_OK;
+  KArgs a{};
+  uint32_t feat = 0;
+  int rc = fill_args(a, lens, batch, opt, rec, newton_stat, status, feat);
+  if (rc) return rc;
+  if ((rc = fill_scat(a, batch, opt, scat, feat))) return rc;
+  a.in = *rays_in;
+  a.out = *rays_out;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = init_outputs(a, s))) return rc;
+  return launch(a, feat, s);
+}
+
+int ort_bsdf_scatter(const double* L, const double* M, const double* N, const double* nx,
+                     const double* ny, const double* nz, int64_t n, int32_t surface_index,
+                     const ort_bsdf* bsdf, const ort_scatter* scat, double* out_L,
+                     double* out_M, double* out_N, int32_t* status, void* stream) {
+  if (!bsdf || !scat || n < 0 || surface_index < 0) return ORT_ERR_ARG;
+  if (bsdf->kind != ORT_BSDF_LAMBERTIAN && bsdf->kind != ORT_BSDF_GAUSSIAN) return ORT_ERR_ARG;
+  if (scat->max_attempts < 1 || scat->ray_offset < 0) return ORT_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (status && hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess)
+    return ORT_ERR_LAUNCH;
+  if (n == 0) return ORT_OK;
+  if (!L || !M || !N || !nx || !ny || !nz || !out_L || !out_M || !out_N) return ORT_ERR_ARG;
+  if ((n + kBlock - 1) / kBlock > 0x7fffffff) return ORT_ERR_ARG;
+  launch_bsdf_scatter(L, M, N, nx, ny, nz, n, surface_index, *bsdf, scat->seed,
+                      scat->ray_offset, scat->max_attempts, out_L, out_M, out_N, status, s);
+  return hipGetLastError() == hipSuccess ? ORT_OK : ORT_ERR_LAUNCH;
+}
+
 }  // extern "C"
 
 namespace ortk {
@@ -163,7 +213,7 @@ namespace ortk {
 int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
                      ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
                      double* rec, ort_newton_stat* newton_stat, int32_t* status, void* stream,
-                     SpotFuse* fuse, const ort_polarization* pol) {
+                     SpotFuse* fuse, const ort_polarization* pol, const ort_scatter* scat) {
   if (fuse) fuse->fused = false;
   if (!rays_out || !batch) return ORT_ERR_ARG;
   if (batch->n_rays == 0) return ORT_OK;
@@ -179,6 +229,10 @@ int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
   if (pol) {  // ort_trace_pupil_polarized
     if (fuse) return ORT_ERR_ARG;
     if ((rc = fill_pol(a, batch, opt, pol, feat))) return rc;
+  }
+  if (scat) {  // ort_trace_pupil_scatter
+    if (fuse || pol) return ORT_ERR_ARG;
+    if ((rc = fill_scat(a, batch, opt, scat, feat))) return rc;
   }
   if (opt->tape) {  // the adjoint tape of a differentiable trace (Newton lenses)
     if ((feat & F_KM) == 0 || (feat & (F_REC | F_IA | F_WRAY)) != 0 ||

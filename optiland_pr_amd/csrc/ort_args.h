@@ -28,6 +28,7 @@
 #include "ort_interact.h"
 #include "ort_material.h"
 #include "ort_polar.h"
+#include "ort_scatter.h"
 
 namespace ortk {
 
@@ -70,6 +71,8 @@ enum : uint32_t {
                      // ort_trace_*_polarized)
   F_PLAIN = 1u << 15,  // ORT_LENS_PLAIN: planes and conics only, no aperture, mirror or
                        // recorded surface (closed-form kernels: the fast pass's plain form)
+  F_SCAT = 1u << 17,  // BSDF scattering after the interaction (ort_scatter.h,
+                      // ort_trace_*_scatter); bit 16 is ort::KM_NURBS
 };
 // every Newton kind compiled in: the host library's one specialisation (the GPU's per-lens
 // KM specialisations only prune code: the values are the same)
@@ -165,6 +168,12 @@ struct KArgs {
   int32_t pol_mode;
   ort::Cplx pol_ex, pol_ey;
   double* p_out;
+  // F_SCAT (ort_scatter): the surfaces' BSDFs and the random stream's seed, ray offset and
+  // attempt cap
+  const ort_bsdf* bsdf;
+  uint64_t scat_seed;
+  int64_t scat_offset;
+  int32_t scat_max;
 };
 
 // ort_trace_*_polarized: the checks beyond fill_args and the F_POL arguments. Lenses with
@@ -181,6 +190,21 @@ inline int fill_pol(KArgs& a, const ort_batch* batch, const ort_options* opt,
   a.pol_ey = {pol->ey_re, pol->ey_im};
   a.p_out = pol->p_out;
   feat |= F_POL;
+  return ORT_OK;
+}
+
+// ort_trace_*_scatter: the checks beyond fill_args and the F_SCAT arguments, with the same
+// refusals as fill_pol (the scatter step sits in the refractive / reflective surface step).
+inline int fill_scat(KArgs& a, const ort_batch* batch, const ort_options* opt,
+                     const ort_scatter* scat, uint32_t& feat) {
+  if (!scat || !scat->bsdf || batch->w || opt->tape || opt->rms_part) return ORT_ERR_ARG;
+  if (scat->max_attempts < 1 || scat->ray_offset < 0) return ORT_ERR_ARG;
+  if (feat & (F_IA | F_WRAY | ort::KM_NURBS)) return ORT_ERR_ARG;
+  a.bsdf = scat->bsdf;
+  a.scat_seed = scat->seed;
+  a.scat_offset = scat->ray_offset;
+  a.scat_max = scat->max_attempts;
+  feat = (feat | F_SCAT) & ~F_PLAIN;  // never the closed-form kernels' fast pass
   return ORT_OK;
 }
 
@@ -409,6 +433,28 @@ ORT_INLINE void pol_step(const KArgs& a, const ort_surface& s, const ort_surface
     n2 = tab(a.n_tab, a.n_lambda, a.n_mat, lam, ct.mat_post);
   }
   ort::pol_surface(pol, ct, refl, nx, ny, nz, k0x, k0y, k0z, r.L, r.M, r.N, n1, n2, r.i);
+}
+
+// F_SCAT: the step of a refractive / reflective surface si at the hit point -- interact()'s
+// operations on the ray with the raw normal kept, then the BSDF of the surface (kind NONE:
+// nothing more, so the ray is the plain trace's). rid: the ray's index in the batch.
+// Returns the status bits to raise. hn, nx, ny, nz: as pol_step.
+template <uint32_t KM>
+ORT_INLINE int scat_step(const KArgs& a, const ort_surface& s, const ort_surface_optics& o,
+                         int si, int64_t rid, ort::Ray& r, bool hn, double& nx, double& ny,
+                         double& nz) {
+  if (!hn)
+    ort::surface_normal<KM>(s, s.radius, s.conic, cst(a.coef), cst(a.zern), kNoSeed, r, nx, ny,
+                            nz);
+  if (s.flags & ORT_SURF_REFLECTIVE)
+    ort::reflect(r, nx, ny, nz);
+  else
+    ort::refract(r, nx, ny, nz, o.u);
+  const ort_bsdf f = cst(a.bsdf)[si];
+  if (f.kind == ORT_BSDF_NONE) return 0;
+  const bool ok = ort::bsdf_scatter(f, a.scat_seed, (uint64_t)(rid + a.scat_offset),
+                                    (uint32_t)si, a.scat_max, nx, ny, nz, r.L, r.M, r.N);
+  return ok ? 0 : (int)ORT_STATUS_SCATTER_ATTEMPTS;
 }
 
 // The caller's ray r_ld (traces of resident rays).

@@ -165,6 +165,13 @@ void trace_group(const KArgs& a, int64_t r0, int64_t r1, int32_t* updates, int& 
       if (a.coat) {  // trace_kernel<F_POL>'s step (refractive / reflective surfaces only)
         double ux, uy, uz;
         pol_step<kAllKinds>(a, s, o, si, lam[k], r, pol[k], false, ux, uy, uz);
+      } else if (a.bsdf) {  // trace_kernel<F_SCAT>'s step
+        double ux, uy, uz;
+        const int bits = scat_step<kAllKinds>(a, s, o, si, r0 + k, r, false, ux, uy, uz);
+        if (bits) {
+#pragma omp atomic
+          status |= bits;
+        }
       } else if (a.w)
         interact<kAllKinds, true>(a, s, r, o, lam[k], wl[k], un);
       else
@@ -290,7 +297,8 @@ void ort_host_set_threads(int32_t n) { g_threads = n; }
 static int host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
                                  ort_rays* rays_out, const ort_batch* batch,
                                  const ort_options* opt, double* rec, int32_t* updates,
-                                 int32_t* status, const ort_polarization* pol) {
+                                 int32_t* status, const ort_polarization* pol,
+                                 const ort_scatter* scat = nullptr) {
   if (!rays_in || !rays_out || !batch) return ORT_ERR_ARG;
   const ort_options dflt{ORT_NEWTON_SCHEDULE, 0, nullptr, 0, 0};
   if (!opt) opt = &dflt;
@@ -300,6 +308,7 @@ static int host_trace_sequential(const ort_lens* lens, const ort_rays* rays_in,
   int rc = fill_args(a, lens, batch, opt, rec, nullptr, status, feat);
   if (rc) return rc;
   if (pol && (rc = fill_pol(a, batch, opt, pol, feat))) return rc;
+  if (scat && (rc = fill_scat(a, batch, opt, scat, feat))) return rc;
   a.in = *rays_in;
   a.out = *rays_out;
   if (status) *status = 0;
@@ -321,6 +330,42 @@ int ort_host_trace_sequential_polarized(const ort_lens* lens, const ort_rays* ra
                                         int32_t* status, const ort_polarization* pol) {
   if (!pol) return ORT_ERR_ARG;
   return host_trace_sequential(lens, rays_in, rays_out, batch, opt, rec, updates, status, pol);
+}
+
+int ort_host_trace_sequential_scatter(const ort_lens* lens, const ort_rays* rays_in,
+                                      ort_rays* rays_out, const ort_batch* batch,
+                                      const ort_options* opt, double* rec, int32_t* updates,
+                                      int32_t* status, const ort_scatter* scat) {
+  if (!scat) return ORT_ERR_ARG;
+  return host_trace_sequential(lens, rays_in, rays_out, batch, opt, rec, updates, status,
+                               nullptr, scat);
+}
+
+int ort_host_bsdf_scatter(const double* L, const double* M, const double* N, const double* nx,
+                          const double* ny, const double* nz, int64_t n, int32_t surface_index,
+                          const ort_bsdf* bsdf, const ort_scatter* scat, double* out_L,
+                          double* out_M, double* out_N, int32_t* status) {
+  if (!bsdf || !scat || n < 0 || surface_index < 0) return ORT_ERR_ARG;
+  if (bsdf->kind != ORT_BSDF_LAMBERTIAN && bsdf->kind != ORT_BSDF_GAUSSIAN) return ORT_ERR_ARG;
+  if (scat->max_attempts < 1 || scat->ray_offset < 0) return ORT_ERR_ARG;
+  if (status) *status = 0;
+  if (n == 0) return ORT_OK;
+  if (!L || !M || !N || !nx || !ny || !nz || !out_L || !out_M || !out_N) return ORT_ERR_ARG;
+  int st = 0;
+  const int nt = threads_for(n);
+#pragma omp parallel for num_threads(nt) schedule(static) reduction(| : st)
+  for (int64_t r = 0; r < n; ++r) {
+    double l = L[r], m = M[r], k = N[r];
+    if (!ort::bsdf_scatter(*bsdf, scat->seed, (uint64_t)(r + scat->ray_offset),
+                           (uint32_t)surface_index, scat->max_attempts, nx[r], ny[r], nz[r], l,
+                           m, k))
+      st |= ORT_STATUS_SCATTER_ATTEMPTS;
+    out_L[r] = l;
+    out_M[r] = m;
+    out_N[r] = k;
+  }
+  if (status) *status = st;
+  return ORT_OK;
 }
 
 }  // extern "C"
@@ -468,7 +513,7 @@ int ort_host_trace_sequential_vjp(const ort_lens* lens, const ort_rays* rays_in,
 static int host_trace_pupil(const ort_lens* lens, const double* px, const double* py,
                             ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
                             double* rec, int32_t* updates, int32_t* status,
-                            const ort_polarization* pol) {
+                            const ort_polarization* pol, const ort_scatter* scat = nullptr) {
   if (!px || !py || !rays_out || !batch || !batch->seg || batch->n_seg < 1 || batch->w)
     return ORT_ERR_ARG;
   const ort_options dflt{ORT_NEWTON_SCHEDULE, 0, nullptr, 0, 0};
@@ -479,6 +524,7 @@ static int host_trace_pupil(const ort_lens* lens, const double* px, const double
   int rc = fill_args(a, lens, batch, opt, rec, nullptr, status, feat);
   if (rc) return rc;
   if (pol && (rc = fill_pol(a, batch, opt, pol, feat))) return rc;
+  if (scat && (rc = fill_scat(a, batch, opt, scat, feat))) return rc;
   if (batch->n_rays != (int64_t)batch->n_seg * batch->seg_len) return ORT_ERR_ARG;
   a.out = *rays_out;
   if (status) *status = 0;
@@ -504,6 +550,15 @@ int ort_host_trace_pupil_polarized(const ort_lens* lens, const double* px, const
                                    int32_t* status, const ort_polarization* pol) {
   if (!pol) return ORT_ERR_ARG;
   return host_trace_pupil(lens, px, py, rays_out, batch, opt, rec, updates, status, pol);
+}
+
+int ort_host_trace_pupil_scatter(const ort_lens* lens, const double* px, const double* py,
+                                 ort_rays* rays_out, const ort_batch* batch,
+                                 const ort_options* opt, double* rec, int32_t* updates,
+                                 int32_t* status, const ort_scatter* scat) {
+  if (!scat) return ORT_ERR_ARG;
+  return host_trace_pupil(lens, px, py, rays_out, batch, opt, rec, updates, status, nullptr,
+                          scat);
 }
 
 int ort_host_generate_rays(const double* px, const double* py, ort_rays* rays_out,

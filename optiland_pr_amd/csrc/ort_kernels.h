@@ -73,7 +73,8 @@ struct SpotFuse {
 int trace_pupil_impl(const ort_lens* lens, const double* px, const double* py,
                      ort_rays* rays_out, const ort_batch* batch, const ort_options* opt,
                      double* rec, ort_newton_stat* newton_stat, int32_t* status, void* stream,
-                     SpotFuse* fuse, const ort_polarization* pol = nullptr);
+                     SpotFuse* fuse, const ort_polarization* pol = nullptr,
+                     const ort_scatter* scat = nullptr);
 
 // Ray of this thread when every (field, lambda) segment traces the SAME pupil samples
 // (real_ray_tracer.py:74-77 field-major layout: ray = segment * seg_len + p): block b
@@ -520,7 +521,7 @@ __device__ inline __attribute__((always_inline)) double newton_distance(const KA
 template <uint32_t FEAT>
 constexpr bool kNewtonFast =
     (FEAT & F_KM) != 0 && (FEAT & F_KM & ~(ort::KM_EVEN | ort::KM_ODD)) == 0 &&
-    (FEAT & (F_IA | F_WRAY | F_TAPE | F_POL)) == 0;
+    (FEAT & (F_IA | F_WRAY | F_TAPE | F_POL | F_SCAT)) == 0;
 
 // The verify rounds' grid-stride form (F_STRIDE) usually returns at once and re-traces
 // only after a schedule correction: 2 waves per SIMD, so it carries no scratch (its
@@ -529,6 +530,9 @@ constexpr bool kNewtonFast =
 // polarization matrix, the initial direction and intensity) on top of the all-kinds Newton
 // kernel: see DESIGN.md section 12 for the compiler's figures behind this choice.
 constexpr int kPolWaves = 2;
+// trace_kernel<F_SCAT> (ort_k_trace_scat.hip) is the all-kinds Newton kernel plus the
+// scatter step, whose Philox state is integer and transient and whose tangent frame lives
+// only inside the step: the compiler's choice of registers is kept.
 template <uint32_t FEAT>
 struct TraceWaves {
   static constexpr int value =
@@ -917,6 +921,11 @@ __device__ __forceinline__ void trace_block(const KArgs& a, const int32_t* sched
       to_intersection(a, s, r, t, alpha, n_pre);
       double nx = hnx, ny = hny, nz = hnz;
       pol_step<(FEAT & F_KM)>(a, s, o, si, lam, r, pol, hn, nx, ny, nz);
+    } else if constexpr ((FEAT & F_SCAT) != 0) {
+      // the generic step below with the raw normal kept for the surface's BSDF
+      to_intersection(a, s, r, t, alpha, n_pre);
+      double nx = hnx, ny = hny, nz = hnz;
+      range_bits |= scat_step<(FEAT & F_KM)>(a, s, o, si, r_ld, r, hn, nx, ny, nz);
     } else if constexpr ((FEAT & F_KM) != 0) {
       if (hn) {  // finish_surface with the normal of the last Newton evaluation
         to_intersection(a, s, r, t, alpha, n_pre);
@@ -1423,8 +1432,14 @@ KernelFn select_trace_mono(uint32_t feat); // Newton lenses, F_GEN, wave-uniform
                                            // (ort_k_trace_mono.hip)
 KernelFn select_trace_ia(uint32_t feat);   // thin-lens / phase / grating lenses (ort_k_trace_ia.hip)
 KernelFn select_trace_tape(uint32_t feat); // Newton lenses, F_GEN, writing the adjoint tape
-KernelFn select_trace_pol(uint32_t feat);  // coated / polarized lenses          (ort_k_trace_pol.hip)
                                            // (ort_k_trace_tape.hip)
+KernelFn select_trace_pol(uint32_t feat);  // coated / polarized lenses          (ort_k_trace_pol.hip)
+KernelFn select_trace_scat(uint32_t feat); // lenses with BSDF surfaces          (ort_k_trace_scat.hip)
+// ort_bsdf_scatter: one ray per lane                                       (ort_k_trace_scat.hip)
+void launch_bsdf_scatter(const double* L, const double* M, const double* N, const double* nx,
+                         const double* ny, const double* nz, int64_t n, int32_t surface,
+                         ort_bsdf f, uint64_t seed, int64_t ray_offset, int32_t max_attempts,
+                         double* oL, double* oM, double* oN, int32_t* status, hipStream_t stream);
 // n(w), k(w) of one material (ort_material_nk)                            (ort_k_closed.hip)
 void launch_material_nk(const ort_material* mats, const double* coef, int32_t mat,
                         const double* w, int64_t n, double* n_out, double* k_out,

@@ -52,6 +52,7 @@ def trace_sharded(optic, fields, wavelengths, px, py, group=None, newton_mode="r
     n_p = len(px)
     a, b = shard_range(n_p, rank, world)
     dl = lens_for(optic, list(wavelengths))
+    _refuse_bsdf(dl, "trace_sharded")
     dev = dl.device
     EPL, EPD = pupil_scalars(optic)
     segs = np.stack([segment_params(optic, float(hx), float(hy), wi, EPL, EPD)
@@ -68,6 +69,14 @@ def trace_sharded(optic, fields, wavelengths, px, py, group=None, newton_mode="r
         if dl.newton and world > 1 and newton_mode != "wave":
             _agree_newton_schedule(dl, keys, segs, pxl, pyl, out, n, n_loc, group)
     return out, n_loc
+
+
+def _refuse_bsdf(dl, what):
+    """The sharded traces number each rank's rays from 0, so a lens with BSDF surfaces would
+    draw the same random numbers on every rank without any sign of it: refused."""
+    if dl.table.has_bsdf:
+        raise ValueError(f"{what}: lenses with BSDF surfaces are not traced sharded (every "
+                         "shard would reuse the random numbers of ray offset 0)")
 
 
 def _agree_newton_schedule(dl, keys, segs, px, py, out, n, n_loc, group):
@@ -227,6 +236,7 @@ class PipelinedImageTrace:
 
         if dlens.newton:
             raise ValueError("PipelinedImageTrace: lenses without Newton surfaces only")
+        _refuse_bsdf(dlens, "PipelinedImageTrace")
         self.dl, self.gather = dlens, gather
         n_pairs, nl = gather.n_pairs, gather.local
         n = n_pairs * nl

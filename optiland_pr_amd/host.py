@@ -86,7 +86,7 @@ class HostLens:
         return t
 
 
-def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec):
+def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec, ray_offset=0):
     """ort_host_trace_sequential of resident CPU rays (8 contiguous float64 tensors):
     returns the 8 output tensors and the Newton update counts [S] (int32 tensor) the
     reference's stop rule made."""
@@ -105,12 +105,39 @@ def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec):
     status = np.zeros(1, dtype=np.int32)
     opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
     rin_c, out_c = rays_struct(rays_in), rays_struct(outs)
+    if hl.table.has_bsdf:  # ort_host_trace_sequential_scatter (ray r draws as r + ray_offset)
+        if per_ray_w:
+            raise ValueError("BSDF surfaces trace one wavelength per call")
+        scat = _scatter_struct(hl, ray_offset)
+        rc = lib.ort_host_trace_sequential_scatter(
+            C.byref(hl.c), C.byref(rin_c), C.byref(out_c), C.byref(batch), C.byref(opt),
+            addr(rec), addr(updates), addr(status), C.byref(scat[0]))
+        _native.check(rc, "ort_host_trace_sequential_scatter")
+        _raise_scatter_status(hl, scat, int(status[0]))
+        return outs, updates
     rc = lib.ort_host_trace_sequential(C.byref(hl.c), C.byref(rin_c), C.byref(out_c),
                                        C.byref(batch), C.byref(opt), addr(rec),
                                        addr(updates), addr(status))
     _native.check(rc, "ort_host_trace_sequential")
     _raise_status_value(int(status[0]))
     return outs, updates
+
+
+def _scatter_struct(hl, ray_offset):
+    from . import scatter
+
+    return scatter.scatter_struct(hl, ray_offset)
+
+
+def _raise_scatter_status(hl, scat, status):
+    """_raise_status_value, a used-up rejection loop reported by surface and sigma."""
+    from . import scatter
+    from .raytrace import _raise_status_value
+
+    try:
+        _raise_status_value(status)
+    except scatter.ScatterAttemptsError:
+        raise scatter.attempts_error(scatter.describe(hl.table), scat[0].max_attempts) from None
 
 
 def trace_sequential_vjp(hl: HostLens, rays_in, w, per_ray_w, start_surface, sched, tabs,
@@ -136,7 +163,8 @@ def trace_sequential_vjp(hl: HostLens, rays_in, w, per_ray_w, start_surface, sch
     del w_keep
 
 
-def trace_pupil(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, apod=None):
+def trace_pupil(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, apod=None, ray_offset=0,
+                rec=None):
     """ort_host_trace_pupil: rays generated from the pupil samples by the segments (SEGMENT
     records as a uint8 CPU tensor) and traced as one reference trace call (one Newton
     group); returns the 8 output tensors and the update counts [S] (int32)."""
@@ -153,6 +181,14 @@ def trace_pupil(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, apod=None)
     status = np.zeros(1, dtype=np.int32)
     opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
     out_c = rays_struct(outs)
+    if hl.table.has_bsdf:  # ort_host_trace_pupil_scatter (rec: [n_rec][8][n] or None)
+        scat = _scatter_struct(hl, ray_offset)
+        rc = lib.ort_host_trace_pupil_scatter(
+            C.byref(hl.c), addr(px), addr(py), C.byref(out_c), C.byref(batch), C.byref(opt),
+            addr(rec), addr(updates), addr(status), C.byref(scat[0]))
+        _native.check(rc, "ort_host_trace_pupil_scatter")
+        _raise_scatter_status(hl, scat, int(status[0]))
+        return outs, updates[:n_groups * S]
     rc = lib.ort_host_trace_pupil(C.byref(hl.c), addr(px), addr(py), C.byref(out_c),
                                   C.byref(batch), C.byref(opt), addr(updates), addr(status))
     _native.check(rc, "ort_host_trace_pupil")

@@ -127,8 +127,8 @@ class RadialPhaseProfile(BasePhaseProfile):
 # interaction models (optiland/interactions)
 # --------------------------------------------------------------------------------------
 class BaseInteractionModel:
-    """interactions/base.py:24-128 (BSDF scattering is out of scope; a coating is applied
-    by the trace kernels, csrc/ort_polar.h)."""
+    """interactions/base.py:24-128 (a coating and a BSDF are applied by the trace kernels,
+    csrc/ort_polar.h and csrc/ort_scatter.h)."""
 
     interaction_id = _abi.IA_REFRACT_REFLECT
     _registry: dict = {}
@@ -139,7 +139,10 @@ class BaseInteractionModel:
 
     def __init__(self, parent_surface=None, is_reflective=False, coating=None, bsdf=None):
         if bsdf is not None:
-            raise ValueError("BSDF scattering is out of scope for the trace core")
+            from .scatter import BaseBSDF
+
+            if not isinstance(bsdf, BaseBSDF):
+                raise ValueError("bsdf must be a BaseBSDF (scatter.py)")
         if coating is not None:
             from .polarization import BaseCoating
 
@@ -148,14 +151,15 @@ class BaseInteractionModel:
         self.parent_surface = parent_surface
         self.is_reflective = bool(is_reflective)
         self.coating = coating
-        self.bsdf = None
+        self.bsdf = bsdf
 
     def flip(self):
         pass
 
     def to_dict(self):
         return {"type": type(self).__name__, "is_reflective": self.is_reflective,
-                "coating": self.coating.to_dict() if self.coating else None, "bsdf": None}
+                "coating": self.coating.to_dict() if self.coating else None,
+                "bsdf": self.bsdf.to_dict() if self.bsdf else None}
 
     @classmethod
     def from_dict(cls, data, parent_surface=None):
@@ -164,8 +168,9 @@ class BaseInteractionModel:
             raise ValueError(f"Unknown interaction model type: {data.get('type')}")
         kw = {k: v for k, v in data.items() if k not in ("type", "material_pre")}
         if kw.get("bsdf"):
-            raise ValueError("BSDF scattering is out of scope for the trace core")
-        kw.pop("bsdf", None)
+            kw["bsdf"] = bsdf_from_dict(kw["bsdf"])
+        else:
+            kw.pop("bsdf", None)
         if kw.get("coating"):
             kw["coating"] = coating_from_dict(kw["coating"])
         else:
@@ -189,6 +194,16 @@ def coating_from_dict(data):
         return BaseCoating.from_dict(data)
     except (KeyError, TypeError) as e:
         raise ValueError(f"invalid coating dictionary {data!r}: missing or unknown {e}") from e
+
+
+def bsdf_from_dict(data):
+    """BaseBSDF.from_dict with malformed dictionaries reported as ValueError."""
+    from .scatter import BaseBSDF
+
+    try:
+        return BaseBSDF.from_dict(data)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"invalid bsdf dictionary {data!r}: missing or unknown {e}") from e
 
 
 class RefractiveReflectiveModel(BaseInteractionModel):
@@ -261,18 +276,18 @@ class DiffractiveInteractionModel(RefractiveReflectiveModel):
 
 
 def make_interaction(interaction_type, is_reflective, focal_length=None, phase_profile=None,
-                     coating=None):
+                     coating=None, bsdf=None):
     """surfaces/factories/interaction_model_factory.py:29-90."""
     if interaction_type == "refractive_reflective":
-        return RefractiveReflectiveModel(is_reflective=is_reflective, coating=coating)
+        return RefractiveReflectiveModel(is_reflective=is_reflective, coating=coating, bsdf=bsdf)
     if interaction_type == "thin_lens":
         return ThinLensInteractionModel(focal_length=focal_length, is_reflective=is_reflective,
-                                        coating=coating)
+                                        coating=coating, bsdf=bsdf)
     if interaction_type == "diffractive":
-        return DiffractiveInteractionModel(is_reflective=is_reflective, coating=coating)
+        return DiffractiveInteractionModel(is_reflective=is_reflective, coating=coating, bsdf=bsdf)
     if interaction_type == "phase":
         if phase_profile is None:
             raise ValueError("phase_profile is required for phase interaction.")
         return PhaseInteractionModel(phase_profile=phase_profile, is_reflective=is_reflective,
-                                     coating=coating)
+                                     coating=coating, bsdf=bsdf)
     raise ValueError(f"Unknown interaction_type: {interaction_type}")

@@ -40,7 +40,12 @@ from .geometries import (
     ZernikePolynomialGeometry,
     scalar,
 )
-from .interactions import BaseInteractionModel, RefractiveReflectiveModel, coating_from_dict
+from .interactions import (
+    BaseInteractionModel,
+    RefractiveReflectiveModel,
+    bsdf_from_dict,
+    coating_from_dict,
+)
 from .materials import AbbeMaterial, IdealMaterial, Material
 from .apertures import BaseAperture
 from .surfaces import ObjectSurface, Surface
@@ -256,8 +261,6 @@ def optic_from_dict(data):
     sg = optic.surface_group
     prev = None
     for k, sd in enumerate(data["surface_group"]["surfaces"]):
-        if sd.get("bsdf"):
-            raise ValueError(f"surface {k}: bsdf is out of scope for the trace core")
         geometry = geometry_from_dict(sd["geometry"])
         post = material_from_dict(sd["material_post"])
         if sd.get("type") == "ObjectSurface" or k == 0:
@@ -274,6 +277,8 @@ def optic_from_dict(data):
                      RefractiveReflectiveModel(is_reflective=bool(sd.get("is_reflective", False))))
             if sd.get("coating"):  # standard_surface.py:359-366: the surface's own entry
                 model.coating = coating_from_dict(sd["coating"])
+            if sd.get("bsdf"):  # likewise the surface's own bsdf entry
+                model.bsdf = bsdf_from_dict(sd["bsdf"])
             s = Surface(prev, post, geometry, is_stop=bool(sd.get("is_stop", False)),
                         aperture=aperture, surface_type=sd.get("surface_type"),
                         interaction_model=model)
@@ -327,7 +332,8 @@ def optic_to_dict(optic):
         if not isinstance(s, ObjectSurface):
             d.update(material_pre=material_to_dict(s.material_pre), is_stop=bool(s.is_stop),
                      aperture=None if s.aperture is None else s.aperture.to_dict(),
-                     coating=s.coating.to_dict() if s.coating else None, bsdf=None,
+                     coating=s.coating.to_dict() if s.coating else None,
+                     bsdf=s.bsdf.to_dict() if s.bsdf else None,
                      is_reflective=bool(s.is_reflective),
                      surface_type=s.surface_type,
                      interaction_model=s.interaction_model.to_dict())

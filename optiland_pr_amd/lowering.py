@@ -55,6 +55,8 @@ class LensTable:
     # one _abi.COATING record per traced surface (ort_polarization.coatings); a
     # FresnelCoating's own materials are columns of n_tab
     coatings: np.ndarray = None
+    # one _abi.BSDF record per traced surface (ort_scatter.bsdf)
+    bsdf: np.ndarray = None
 
     @property
     def n_surfaces(self):
@@ -116,9 +118,18 @@ class LensTable:
 
     @property
     def has_range_check(self):
-        """Surfaces whose sag raises on out-of-range normalised coordinates."""
+        """The launch's status word must be read back: surfaces whose sag raises on
+        out-of-range normalised coordinates (ORT_STATUS_ZERNIKE_RANGE / CHEBYSHEV_RANGE), or
+        BSDF surfaces, whose rejection loop may use up its attempts
+        (ORT_STATUS_SCATTER_ATTEMPTS)."""
         g = self.surfaces["geometry"]
-        return bool(np.any((g == _abi.GEOM_ZERNIKE) | (g == _abi.GEOM_CHEBYSHEV)))
+        return bool(np.any((g == _abi.GEOM_ZERNIKE) | (g == _abi.GEOM_CHEBYSHEV))) or \
+            self.has_bsdf
+
+    @property
+    def has_bsdf(self):
+        """Some surface scatters (the table goes to ort_trace_*_scatter)."""
+        return self.bsdf is not None and bool(np.any(self.bsdf["kind"] != _abi.BSDF_NONE))
 
     def fingerprint(self):
         """Bytes of everything the device reads: equal fingerprints trace identically."""
@@ -131,6 +142,8 @@ class LensTable:
             parts.append(np.ascontiguousarray(self.apod).tobytes())
         if self.coatings is not None and np.any(self.coatings["kind"] != _abi.COAT_NONE):
             parts.append(np.ascontiguousarray(self.coatings).tobytes())
+        if self.has_bsdf:
+            parts.append(np.ascontiguousarray(self.bsdf).tobytes())
         return b"".join(parts)
 
 
@@ -187,13 +200,15 @@ def _material_n_alpha(m, w):
 
 
 def lower_surface_group(surface_group, wavelengths, record=False, skip_object=True,
-                        polarized=False):
+                        polarized=False, scatter=False):
     """Lower every traced surface (index >= 1) of `surface_group`.
 
     record: False, True (all traced surfaces) or an iterable of traced-surface
     indices (0-based within the traced surfaces) to snapshot (standard_surface.py:266-286).
     polarized: the table is for the coated / polarized trace (ort_trace_*_polarized), which
     has no thin-lens, phase, grating or NURBS surfaces: those raise ValueError here.
+    scatter: likewise for the scattering trace (ort_trace_*_scatter) of a lens with BSDF
+    surfaces; coatings together with a BSDF raise too.
     """
     surfs = [s for s in surface_group.surfaces if not isinstance(s, ObjectSurface)]
     if len(surfs) > _abi.MAX_SURFACES:
@@ -223,6 +238,7 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
     ap_progs = []
     ia_blocks = []
     coat_rows = []
+    bsdf_rows = []
     device_coeffs = []
     for si, s in enumerate(surfs):
         g = s.geometry
@@ -318,11 +334,17 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
             else:
                 raise ValueError(f"coating {type(coating).__name__} is not lowered to the "
                                  "trace core (supported: SimpleCoating, FresnelCoating)")
-        if polarized and (row.get("interaction", _abi.IA_REFRACT_REFLECT)
+        bsdf = getattr(im, "bsdf", None)
+        if bsdf is not None:
+            bsdf_rows.append((si, *bsdf.lower()))
+            if coating is not None:
+                raise ValueError(f"surface {si + 1}: a BSDF together with a coating is not "
+                                 "supported")
+        if (polarized or scatter) and (row.get("interaction", _abi.IA_REFRACT_REFLECT)
                           != _abi.IA_REFRACT_REFLECT or g.geometry_id == _abi.GEOM_NURBS):
             raise ValueError(
                 f"surface {si + 1}: thin-lens, phase, grating and NURBS surfaces are not "
-                "supported with coatings or a polarization state")
+                "supported with coatings, a polarization state or BSDF surfaces")
         loc = g.cs.localize_ops()
         glob = g.cs.globalize_ops()
         # localize starts with translate(-t) of the root frame and globalize ends with
@@ -392,6 +414,9 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
     coatings = np.zeros(max(1, len(surfs)), dtype=_abi.COATING)
     for si, kind, mp, mq, tr, rf in coat_rows:
         coatings[si] = (kind, mp, mq, 0, tr, rf)
+    bsdf_tab = np.zeros(max(1, len(surfs)), dtype=_abi.BSDF)
+    for si, kind, sigma in bsdf_rows:
+        bsdf_tab[si] = (kind, 0, sigma)
     table = np.zeros(len(surfs), dtype=_abi.SURFACE)
     for name in {k for row in rows for k in row}:
         table[name] = [row.get(name, 0) for row in rows]
@@ -411,6 +436,7 @@ def lower_surface_group(surface_group, wavelengths, record=False, skip_object=Tr
         rec_surfaces=rec_set,
         device_coeffs=device_coeffs,
         coatings=coatings,
+        bsdf=bsdf_tab,
     )
 
 

@@ -256,13 +256,16 @@ LENS_META = ("n_surfaces", "n_lambda", "n_mat", "final_mat", "geometry_mask",
 NEWTON_MODES = ("reference", "device", "wave")
 
 
-def lens_args(dl):
+def lens_args(dl, scatter=False):
     """(lens, lens_meta, final_thickness, lens_key) of a DeviceLens / HostLens: the nine
     lowered tables as tensors on the lens's device -- surfaces, cs_ops, zern, optics and
     materials as their bytes (uint8), coef, n_tab, alpha_tab and the wavelengths as float64
     -- the ort_lens scalars, the image-space thickness and the handle of the object that
     holds the host-side state (Newton schedule caches), used only as a cache key."""
     t = dl.table
+    if t.has_bsdf and not scatter:  # (scatter: the *_scatter ops, which take the BSDF records)
+        raise ValueError("the lens has BSDF surfaces: the differentiable trace ops do not carry "
+                         "them (Optic.trace, trace_generic and SurfaceGroup.trace do)")
     meta = [int(t.n_surfaces), len(t.wavelengths), int(t.n_tab.shape[1]), int(t.final_mat),
             int(dl.geometry_mask), int(t.interaction_mask), int(t.frame_flags), int(t.n_rec),
             1 if dl.newton else 0, tape_rows(t)]
@@ -1260,3 +1263,177 @@ def _polarized_backward(ctx, *grads):
 
 
 trace_pupil_polarized.register_autograd(_polarized_backward)
+
+
+# --------------------------------------------------------------------------------------
+# ort::trace_pupil_scatter / trace_sequential_scatter / bsdf_scatter (BSDF surfaces; forward
+# only)
+# --------------------------------------------------------------------------------------
+def _seed64(seed):
+    """A 64-bit seed as the ops carry it (a signed 64-bit int: two's complement)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+def scatter_args(lens, segs, px, py, n, seg_len, pupil_per_ray=False, ray_offset=0):
+    """The arguments of torch.ops.ort.trace_pupil_scatter for a DeviceLens / HostLens of a
+    table with BSDF surfaces: the lens tensors, its BSDF records and the SEGMENT /
+    APODIZATION records as uint8 tensors on the lens's device, the pupil, the seed
+    (lens.scatter) and plan_meta = [n, seg_len, pupil_per_ray, ray_offset, max_attempts]."""
+    from . import polarization as pz
+    from . import scatter as sc
+
+    L, meta, ft, key = lens_args(lens, scatter=True)
+    dev = lens.device
+    bsdf = lens.resident("bsdf", np.ascontiguousarray(lens.table.bsdf).view(np.uint8))
+    seg = segs if torch.is_tensor(segs) else pz._bytes_tensor(
+        np.asarray(segs, dtype=_abi.SEGMENT)).to(dev)
+    seed, cap = getattr(lens, "scatter", (0, sc.DEFAULT_MAX_ATTEMPTS))
+    return (L, meta, ft, key, bsdf, seg, pz._apod_of(lens), px, py, _seed64(seed),
+            [int(n), int(seg_len), int(bool(pupil_per_ray)), int(ray_offset), int(cap)])
+
+
+def sequential_scatter_args(lens, rays_in, start_surface=0, ray_offset=0):
+    """The arguments of torch.ops.ort.trace_sequential_scatter: rays_in [8, n] (x y z L M N
+    i opd) on the lens's device; plan_meta = [start_surface, ray_offset, max_attempts]."""
+    from . import scatter as sc
+
+    L, meta, ft, key = lens_args(lens, scatter=True)
+    bsdf = lens.resident("bsdf", np.ascontiguousarray(lens.table.bsdf).view(np.uint8))
+    seed, cap = getattr(lens, "scatter", (0, sc.DEFAULT_MAX_ATTEMPTS))
+    return (L, meta, ft, key, bsdf, rays_in, _seed64(seed),
+            [int(start_surface), int(ray_offset), int(cap)])
+
+
+def _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap, apod=None):
+    """The resolved lens carrying the op's BSDF records, seed and attempt cap (a lens
+    rebuilt from its tensors has none of its own)."""
+    dl = _resolve(lens, lens_meta, final_thickness, lens_key)
+    rec = np.frombuffer(bsdf.detach().cpu().numpy().tobytes(), dtype=_abi.BSDF).copy()
+    if dl.table.bsdf is None or dl.table.bsdf.tobytes() != rec.tobytes():
+        dl.table.bsdf = rec
+    dl.scatter = (int(seed) & 0xFFFFFFFFFFFFFFFF, int(cap))
+    if apod is not None and dl.device.type != "cpu" and getattr(dl, "apod", None) is None:
+        dl.apod = apod
+    return dl
+
+
+@torch.library.custom_op("ort::trace_pupil_scatter", mutates_args=(), device_types="cuda")
+def trace_pupil_scatter(lens: list[torch.Tensor], lens_meta: list[int], final_thickness: float,
+                        lens_key: int, bsdf: torch.Tensor, seg: torch.Tensor,
+                        apod: torch.Tensor | None, px: torch.Tensor, py: torch.Tensor,
+                        seed: int, plan_meta: list[int]) -> torch.Tensor:
+    """Optic.trace's fused generation + trace of a lens with BSDF surfaces
+    (ort_trace_pupil_scatter): the rays [8, n] (x y z L M N i opd). Ray r draws as ray
+    r + ray_offset of the stream keyed by `seed`. Forward only: a backward raises."""
+    n, seg_len, ppr, ray_offset, cap = plan_meta[:5]
+    dl = _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap, apod)
+    pxc, pyc = px.detach().contiguous(), py.detach().contiguous()
+    if dl.device.type == "cpu":
+        from . import host
+
+        outs, _ = host.trace_pupil(dl, seg, pxc, pyc, n, seg_len, bool(ppr), apod=apod,
+                                   ray_offset=ray_offset)
+        return torch.stack(outs)
+    from . import raytrace
+
+    rays = torch.empty((8, n), dtype=torch.float64, device=dl.device)
+    out = raytrace.RealRays.__new__(raytrace.RealRays)
+    for a, t in zip(_abi.RAY_FIELDS, rays.unbind(0), strict=True):
+        setattr(out, a, t)
+    raytrace.trace_pupil(dl, seg, pxc, pyc, out, n, seg_len, max(n, 1),
+                         pupil_per_ray=bool(ppr), ray_offset=ray_offset)
+    return rays
+
+
+@trace_pupil_scatter.register_kernel("cpu")
+def _trace_pupil_scatter_cpu(lens, lens_meta, final_thickness, lens_key, bsdf, seg, apod, px,
+                             py, seed, plan_meta):
+    """The CPU dispatch key: the host build (ort_host_trace_pupil_scatter)."""
+    return trace_pupil_scatter._init_fn(lens, lens_meta, final_thickness, lens_key, bsdf, seg,
+                                        apod, px, py, seed, plan_meta)
+
+
+@trace_pupil_scatter.register_fake
+def _(lens, lens_meta, final_thickness, lens_key, bsdf, seg, apod, px, py, seed, plan_meta):
+    return px.new_empty((8, plan_meta[0]), dtype=torch.float64)
+
+
+@torch.library.custom_op("ort::trace_sequential_scatter", mutates_args=(), device_types="cuda")
+def trace_sequential_scatter(lens: list[torch.Tensor], lens_meta: list[int],
+                             final_thickness: float, lens_key: int, bsdf: torch.Tensor,
+                             rays_in: torch.Tensor, seed: int,
+                             plan_meta: list[int]) -> torch.Tensor:
+    """SurfaceGroup.trace of resident rays [8, n] through a lens with BSDF surfaces
+    (ort_trace_sequential_scatter): the traced rays [8, n]. Forward only."""
+    start_surface, ray_offset, cap = plan_meta[:3]
+    dl = _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap)
+    rin = rays_in.detach().to(torch.float64).contiguous()
+    if dl.device.type == "cpu":
+        from . import host
+
+        outs, _ = host.trace_sequential(dl, list(rin.unbind(0)), None, False, start_surface,
+                                        None, ray_offset=ray_offset)
+        return torch.stack(outs)
+    from . import raytrace
+
+    rout = torch.empty_like(rin)
+    src, dst = (raytrace.RealRays.__new__(raytrace.RealRays) for _ in range(2))
+    for a, s, d in zip(_abi.RAY_FIELDS, rin.unbind(0), rout.unbind(0), strict=True):
+        setattr(src, a, s)
+        setattr(dst, a, d)
+    raytrace.trace_rays(dl, src, dst, start_surface=start_surface, ray_offset=ray_offset)
+    return rout
+
+
+@trace_sequential_scatter.register_kernel("cpu")
+def _trace_sequential_scatter_cpu(lens, lens_meta, final_thickness, lens_key, bsdf, rays_in,
+                                  seed, plan_meta):
+    """The CPU dispatch key: the host build (ort_host_trace_sequential_scatter)."""
+    return trace_sequential_scatter._init_fn(lens, lens_meta, final_thickness, lens_key, bsdf,
+                                             rays_in, seed, plan_meta)
+
+
+@trace_sequential_scatter.register_fake
+def _(lens, lens_meta, final_thickness, lens_key, bsdf, rays_in, seed, plan_meta):
+    return rays_in.new_empty(rays_in.shape, dtype=torch.float64)
+
+
+@torch.library.custom_op("ort::bsdf_scatter", mutates_args=(), device_types="cuda")
+def bsdf_scatter(dirs: torch.Tensor, normals: torch.Tensor, kind: int, sigma: float, seed: int,
+                 plan_meta: list[int]) -> torch.Tensor:
+    """BaseBSDF.scatter on tensors (ort_bsdf_scatter): dirs [3, n] (L M N) and normals
+    [3, n] -> the scattered directions [3, n]. kind: _abi.BSDF_LAMBERTIAN / BSDF_GAUSSIAN;
+    plan_meta = [surface_index, ray_offset, max_attempts]. Forward only."""
+    from . import scatter as sc
+
+    f = sc.LambertianBSDF() if kind == _abi.BSDF_LAMBERTIAN else sc.GaussianBSDF(sigma)
+    if kind not in (_abi.BSDF_LAMBERTIAN, _abi.BSDF_GAUSSIAN):
+        raise ValueError("bsdf_scatter: kind must be BSDF_LAMBERTIAN or BSDF_GAUSSIAN")
+    surface_index, ray_offset, cap = plan_meta[:3]
+    d, nrm = dirs.detach(), normals.detach()
+    outs = sc.bsdf_scatter(d[0], d[1], d[2], nrm[0], nrm[1], nrm[2], f,
+                           seed=int(seed) & 0xFFFFFFFFFFFFFFFF, surface_index=surface_index,
+                           ray_offset=ray_offset, max_attempts=cap)
+    return torch.stack(outs)
+
+
+@bsdf_scatter.register_kernel("cpu")
+def _bsdf_scatter_cpu(dirs, normals, kind, sigma, seed, plan_meta):
+    """The CPU dispatch key: the host build (ort_host_bsdf_scatter)."""
+    return bsdf_scatter._init_fn(dirs, normals, kind, sigma, seed, plan_meta)
+
+
+@bsdf_scatter.register_fake
+def _(dirs, normals, kind, sigma, seed, plan_meta):
+    return dirs.new_empty(dirs.shape, dtype=torch.float64)
+
+
+def _scatter_backward(ctx, *grads):
+    raise RuntimeError("the ort::*_scatter ops are forward only: a trace through BSDF "
+                       "surfaces has no derivative")
+
+
+trace_pupil_scatter.register_autograd(_scatter_backward)
+trace_sequential_scatter.register_autograd(_scatter_backward)
+bsdf_scatter.register_autograd(_scatter_backward)

@@ -30,6 +30,10 @@ class Optic:
         self.paraxial = Paraxial(self)
         self.obj_space_telecentric = False
         self.polarization = "ignore"
+        # BSDF surfaces (scatter.py): the 64-bit seed of the counter-based random stream --
+        # the same seed gives the same trace -- and the cap of a ray's rejection draws
+        self.scatter_seed = 0
+        self.scatter_max_attempts = 1024
         self.apodization = None
         self._lowered = None  # lowering cache (raytrace.LoweredLens), reset on edits
         # Newton schedule verification of trace(): "reference" checks each launch's

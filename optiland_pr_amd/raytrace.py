@@ -371,7 +371,16 @@ def lens_for(optic_or_group, wavelengths, record=False, image_record=False, pola
             raise ValueError(
                 "this trace path does not support coatings or a polarization state; "
                 "Optic.trace, Optic.trace_generic and SurfaceGroup.trace do")
-    table = lower_surface_group(sg, wavelengths, record=record, polarized=polarized)
+    from . import scatter as _scatter
+
+    scat = _scatter.has_bsdf(sg)
+    if scat:  # BSDF surfaces: the F_SCAT kernel family (trace_pupil / trace_rays route there)
+        if polarized or getattr(host, "polarization", "ignore") != "ignore":
+            raise ValueError("BSDF surfaces together with coatings or a polarization state "
+                             "are not supported")
+        key = (*key, "scatter")
+    table = lower_surface_group(sg, wavelengths, record=record, polarized=polarized,
+                                scatter=scat)
     table.apod = lower_apodization(host)
     if image_record:
         table.final_mat = -1
@@ -388,6 +397,8 @@ def lens_for(optic_or_group, wavelengths, record=False, image_record=False, pola
     elif table.device_coeffs:  # the cached upload: this call's coefficient tensors + values
         hit.table.device_coeffs = table.device_coeffs
         hit.patch_coefficients(table.device_coeffs)
+    if scat:  # read on every call: a new seed needs no new upload
+        hit.scatter = _scatter.settings_of(host)
     return hit
 
 
@@ -743,6 +754,35 @@ def _raise_status_value(v):
         raise ZernikeRangeError(_ZERNIKE_MSG)
     if v & _abi.STATUS_CHEBYSHEV_RANGE:
         raise ChebyshevRangeError(_CHEBYSHEV_MSG)
+    if v & _abi.STATUS_SCATTER_ATTEMPTS:
+        from .scatter import ScatterAttemptsError
+
+        raise ScatterAttemptsError("BSDF scattering used up its attempts")
+
+
+def _scatter_call(dlens, ray_offset, tape=None, rms=None):
+    """The ort_scatter of a lens with BSDF surfaces (None for any other lens), kept alive
+    with its table; a tape / rms request (a differentiable trace) is refused."""
+    if not dlens.table.has_bsdf:
+        if ray_offset:
+            raise ValueError("ray_offset is the scattering trace's (no BSDF surface here)")
+        return None
+    if tape is not None or rms is not None:
+        raise NotImplementedError("a trace through BSDF surfaces has no derivative")
+    from . import scatter
+
+    return scatter.scatter_struct(dlens, ray_offset)
+
+
+def _run_scatter(dlens, scat, *args, **kw):
+    """_run, with a used-up rejection loop reported by surface and sigma."""
+    from . import scatter
+
+    try:
+        _run(dlens, *args, **kw)
+    except scatter.ScatterAttemptsError:
+        raise scatter.attempts_error(scatter.describe(dlens.table), scat[0].max_attempts) \
+            from None
 
 
 def upload_segments(segments: np.ndarray, device):
@@ -752,8 +792,10 @@ def upload_segments(segments: np.ndarray, device):
 
 def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
                 seg_len, group_len, pupil_per_ray=False, keys=(), rec=None,
-                newton_mode="reference", start_surface=0, tape=None, exact_only=False, rms=None):
-    """Generate + trace in one launch (ort_trace_pupil). `segments` is a host SEGMENT array
+                newton_mode="reference", start_surface=0, tape=None, exact_only=False, rms=None,
+                ray_offset=0):
+    """Generate + trace in one launch (ort_trace_pupil; ort_trace_pupil_scatter for a lens
+    with BSDF surfaces, whose ray r draws as ray r + ray_offset). `segments` is a host SEGMENT array
     or the device tensor returned by upload_segments (no per-call copy). tape: a device
     buffer of ort_vjp_tape_size bytes the launch writes the adjoint tape into (Newton
     lenses; the backward then runs the reverse sweep only). rms: (rms [], stats [5]) device
@@ -776,6 +818,7 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
             raise ValueError("trace_pupil: the fused rms spot size needs the taped forward")
         part = torch.empty(rows * 4, dtype=torch.float64, device=dlens.device)
     part_p = addr(part)
+    scat = _scatter_call(dlens, ray_offset, tape, rms)
 
     def launch(opt, stats, status):
         opt.start_surface = start_surface
@@ -783,8 +826,17 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
         opt.rms_part = part_p
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
+        if scat is not None:
+            rc = lib.ort_trace_pupil_scatter(*args, C.byref(opt), rec_p, addr(stats),
+                                             addr(status), C.byref(scat[0]), stream)
+            _native.check(rc, "ort_trace_pupil_scatter")
+            return
         rc = lib.ort_trace_pupil(*args, C.byref(opt), rec_p, addr(stats), addr(status), stream)
         _native.check(rc, "ort_trace_pupil")
+
+    if scat is not None:
+        _run_scatter(dlens, scat, launch, n_rays, group_len, list(keys), newton_mode)
+        return seg_dev
 
     _run(dlens, launch, n_rays, group_len, list(keys), newton_mode,
          rms=(part, rows, rms[1], rms[0]) if rms is not None and n_rays > 0 else None)
@@ -798,6 +850,11 @@ def trace_spot(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays, seg_l
     if dlens.newton:
         raise ValueError("trace_spot: Newton lenses trace through trace_pupil + "
                          "SpotStatistics.run (the Newton schedule protocol)")
+    if dlens.table.has_bsdf:
+        # the fused epilogue is the closed-form kernels': a lens with BSDF surfaces traces
+        # on the F_SCAT family, then the statistics run on its rays (the same numbers)
+        trace_pupil(dlens, segments, px, py, out, n_rays, seg_len, seg_len)
+        return spot.run(out)
     lib = _native.load()
     seg_dev = (segments if torch.is_tensor(segments) else
                dlens.resident("segments", np.asarray(segments, dtype=_abi.SEGMENT)))
@@ -817,8 +874,10 @@ def trace_spot(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays, seg_l
 
 def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_len=None,
                keys=(), rec=None, newton_mode="reference", start_surface=0, segments=None,
-               seg_len=None, per_ray_w=False, exact_only=False):
-    """Trace resident rays (ort_trace_sequential); rays_out may be rays_in (in place).
+               seg_len=None, per_ray_w=False, exact_only=False, ray_offset=0):
+    """Trace resident rays (ort_trace_sequential; ort_trace_sequential_scatter for a lens
+    with BSDF surfaces, whose ray r draws as ray r + ray_offset); rays_out may be rays_in
+    (in place).
     per_ray_w: n and k per ray from rays_in.w (the lens's material tables) instead of
     the per-wavelength tables. exact_only: ORT_OPT_EXACT (no deferred-check pass; the same
     bits -- for the tests that check exactly that)."""
@@ -833,11 +892,20 @@ def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_l
                                             validate=True)
         batch.w = addr(w_keep)
     in_c, out_c = rays_in.c_struct(), rays_out.c_struct()
+    scat = _scatter_call(dlens, ray_offset)
+    if scat is not None and per_ray_w:
+        raise ValueError("BSDF surfaces trace one wavelength per call")
 
     def launch(opt, stats, status):
         opt.start_surface = start_surface
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
+        if scat is not None:
+            rc = lib.ort_trace_sequential_scatter(
+                C.byref(dlens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
+                addr(rec), addr(stats), addr(status), C.byref(scat[0]), _stream_handle())
+            _native.check(rc, "ort_trace_sequential_scatter")
+            return
         rc = lib.ort_trace_sequential(C.byref(dlens.c), C.byref(in_c), C.byref(out_c),
                                       C.byref(batch), C.byref(opt), addr(rec), addr(stats),
                                       addr(status), _stream_handle())
@@ -849,7 +917,10 @@ def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_l
         for a in (*_abi.RAY_FIELDS, "w"):
             setattr(src, a, getattr(rays_in, a).clone())
         in_c = src.c_struct()
-    _run(dlens, launch, n, group_len, list(keys), newton_mode)
+    if scat is not None:
+        _run_scatter(dlens, scat, launch, n, group_len, list(keys), newton_mode)
+    else:
+        _run(dlens, launch, n, group_len, list(keys), newton_mode)
     del w_keep  # (the launches above are ordered on the stream before any reuse)
     return seg_dev
 
@@ -964,6 +1035,8 @@ class RealRayTracer:
         n = n_p * len(segs)
         keys = [("trace", tuple(np.round(Hx, 15)), tuple(np.round(Hy, 15)), float(wavelength), n_p)]
         if autodiff.wants_grad(optic):
+            if dlens.table.has_bsdf:
+                raise NotImplementedError("a trace through BSDF surfaces has no derivative")
             return self._trace_grad(dlens, segs, px, py, n, n_p, wavelength, keys,
                                     record == "all", newton_mode)
         out = RealRays.empty(n, wavelength, device=dev)
@@ -1116,16 +1189,24 @@ def trace_surface_group(sg, rays: RealRays, skip=0, newton_mode="reference"):
 
     if isinstance(rays, polarization.PolarizedRays) or any(
             s.coating is not None for s in sg.surfaces[1:]):
+        if any(s.bsdf is not None for s in sg.surfaces[1:]):
+            raise ValueError("BSDF surfaces together with coatings or a polarization state "
+                             "are not supported")
         return _trace_surface_group_polarized(sg, rays, skip)
     w = torch.unique(rays.w)
     # one wavelength: n / k from the per-wavelength tables (the common Optic.trace case);
     # several: every ray's own n(w), k(w) from the material tables in the kernel
     per_ray = w.numel() != 1
     wl = float(w[0].item())
-    table = lower_surface_group(sg, [wl], record=(sg.record == "all"))
+    from . import scatter as _scatter
+
+    scat = _scatter.has_bsdf(sg)
+    table = lower_surface_group(sg, [wl], record=(sg.record == "all"), scatter=scat)
     # SurfaceGroup.trace does not include the image-space propagate of RealRayTracer
     table.final_mat = -1
     dlens = DeviceLens(table, device=rays.x.device)
+    if scat:  # SurfaceGroup.scatter_seed / scatter_max_attempts (surfaces.py)
+        dlens.scatter = _scatter.settings_of(sg)
     rec = None
     n = len(rays)
     if sg.record == "all":

@@ -125,6 +125,11 @@ class Surface:
         """standard_surface.py:161-164."""
         return getattr(getattr(self, "interaction_model", None), "coating", None)
 
+    @property
+    def bsdf(self):
+        """standard_surface.py:166-169."""
+        return getattr(getattr(self, "interaction_model", None), "bsdf", None)
+
     def set_fresnel_coating(self):
         """standard_surface.py:260-264."""
         from .polarization import FresnelCoating
@@ -262,6 +267,11 @@ class SurfaceGroup:
         # per-surface snapshots (standard_surface.py:266-286): None = image surface only,
         # "all" = every surface (8 x 8 B per ray per surface of HBM writes)
         self.record = None
+        # BSDF surfaces traced through SurfaceGroup.trace on its own (no Optic): the seed of
+        # the random stream and the cap of a ray's rejection draws (Optic.trace reads the
+        # Optic's scatter_seed / scatter_max_attempts instead)
+        self.scatter_seed = 0
+        self.scatter_max_attempts = 1024
 
     # -- properties (surface_group.py:95-217) --
     @property
@@ -435,8 +445,6 @@ class SurfaceGroup:
             interaction_type = "diffractive"
         elif kw.get("phase_profile") is not None:
             interaction_type = "phase"
-        if kw.get("bsdf") is not None:
-            raise ValueError("bsdf is out of scope for the trace core")
         # coating_factory.py:35-60: a coating object, or "fresnel" (the materials around the
         # surface, known once it is linked: set after construction)
         from .polarization import create_coating
@@ -445,7 +453,8 @@ class SurfaceGroup:
         # linking re-derives the coating: Surface.previous_surface)
         coating = create_coating(kw.get("coating"), material_post, material_post)
         model = make_interaction(interaction_type, is_reflective, focal_length=kw.get("f"),
-                                 phase_profile=kw.get("phase_profile"), coating=coating)
+                                 phase_profile=kw.get("phase_profile"), coating=coating,
+                                 bsdf=kw.get("bsdf"))
         return Surface(None, material_post, geometry, is_stop=is_stop,
                        aperture=kw.get("aperture"), surface_type=surface_type,
                        comment=comment, interaction_model=model)
