@@ -35,7 +35,8 @@ extern "C" {
 int ort_host_abi_version(void);
 
 /* lens->frame_flags: ORT_LENS_AXIAL and ORT_LENS_PLAIN (optiland_rt.h) are both
- * accepted and ignored: the host library has one form of every trace. */
+ * accepted and ignored, as is lens->form_flags (ORT_LENS_SPHERES): the host library has
+ * one form of every trace. */
 
 /* ort_trace_sequential on host memory. updates (nullable): int32 [n_groups][n_surfaces],
  * the Newton updates the reference's stop rule made per (group, surface) (0 for closed-form

@@ -114,6 +114,21 @@ enum ort_lens_flags {
    * gets undefined rays; 0 is always safe. */
   ORT_LENS_PLAIN = 1u << 1
 };
+/* ---- lens-wide facts about the surfaces' forms (ort_lens.form_flags) ----------------
+ * (added without a new version number in the word that was `reserved`: 0 stays valid and
+ * means "make no assumption"; the word is honoured only when it holds known bits alone, so
+ * a producer that does not know it, or never cleared it, gets the kernels it got before.
+ * It is a word of its own, not a third bit of frame_flags, because callers compare
+ * frame_flags whole.) */
+enum ort_lens_form_flags {
+  /* a lens that meets ORT_LENS_PLAIN (which must be set too) and whose every
+   * ORT_GEOM_STANDARD surface is a sphere of finite radius with its seed: conic == 0.0
+   * exactly, no ORT_SURF_RADIUS_INF, and ORT_SURF_TWO_INV_R (every sample objective). The
+   * plain closed-form kernels then make those three per-surface decisions at compile time;
+   * the results are the same bits either way. A caller that sets the bit on a lens that
+   * does not meet it gets undefined rays; 0 is always safe. */
+  ORT_LENS_SPHERES = 1u << 0
+};
 
 /* ---- interaction models (optiland/interactions) ----------------------------------
  * What happens at the surface after the ray reaches it (standard_surface.py:225). The
@@ -317,7 +332,8 @@ typedef struct ort_lens {
                               * and grating interactions use it); may be NULL when      *
                               * interaction_mask has no PHASE / DIFFRACTIVE bit         */
   uint32_t frame_flags;      /* enum ort_lens_flags (0: make no assumption)              */
-  uint32_t reserved;
+  uint32_t form_flags;       /* enum ort_lens_form_flags (0: make no assumption); was   */
+                             /* `reserved`                                              */
 } ort_lens;
 
 /* Ray state, structure of arrays, one double per ray per attribute (device). */

@@ -65,6 +65,7 @@ SURF_SLOPE_INEXACT = 1 << 9  # (v19) the Newton slope is not the sag's derivativ
 SURF_TWO_INV_R = 1 << 10  # a standard surface's norm_radius holds RN(2 / R)
 LENS_AXIAL = 1 << 0  # ort_lens.frame_flags
 LENS_PLAIN = 1 << 1  # planes / conics only, no aperture, mirror or record
+LENS_SPHERES = 1 << 0  # ort_lens.form_flags: a plain lens of planes and seeded spheres only
 
 # enum ort_interaction / ort_phase_kind
 IA_REFRACT_REFLECT = 0

@@ -34,7 +34,7 @@ class ort_lens(C.Structure):
         ("materials", C.c_void_p),
         ("wavelengths", C.c_void_p),
         ("frame_flags", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("form_flags", C.c_uint32),  # "reserved" before ORT_LENS_SPHERES (0 stays valid)
     ]
 
 

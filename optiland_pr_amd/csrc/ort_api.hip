@@ -44,6 +44,7 @@ int launch(const KArgs& a_in, uint32_t feat, hipStream_t stream) {
   const bool pol = (feat & F_POL) != 0;
   const bool own_family = pol || scat;
   const bool closed = !own_family && (feat & F_IA) == 0 && (feat & F_KM) == 0;
+  if (!closed) feat &= ~F_SPHERES;  // the closed-form kernels' bit alone
   KernelFn fn = scat               ? select_trace_scat(feat)
                 : pol              ? select_trace_pol(feat)
                 : (feat & F_IA) != 0 ? select_trace_ia(feat & ~F_AXIAL)

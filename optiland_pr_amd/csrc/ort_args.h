@@ -73,6 +73,10 @@ enum : uint32_t {
                        // recorded surface (closed-form kernels: the fast pass's plain form)
   F_SCAT = 1u << 17,  // BSDF scattering after the interaction (ort_scatter.h,
                       // ort_trace_*_scatter); bit 16 is ort::KM_NURBS
+  F_SPHERES = 1u << 18,  // ORT_LENS_SPHERES beside F_PLAIN: every standard surface a seeded
+                         // sphere of finite radius (closed-form kernels: the plain form with
+                         // those uniform decisions compiled in; select_closed drops the bit
+                         // wherever it drops F_PLAIN)
 };
 // every Newton kind compiled in: the host library's one specialisation (the GPU's per-lens
 // KM specialisations only prune code: the values are the same)
@@ -204,7 +208,7 @@ inline int fill_scat(KArgs& a, const ort_batch* batch, const ort_options* opt,
   a.scat_seed = scat->seed;
   a.scat_offset = scat->ray_offset;
   a.scat_max = scat->max_attempts;
-  feat = (feat | F_SCAT) & ~F_PLAIN;  // never the closed-form kernels' fast pass
+  feat = (feat | F_SCAT) & ~(F_PLAIN | F_SPHERES);  // never the closed-form kernels' fast pass
   return ORT_OK;
 }
 
@@ -290,6 +294,9 @@ inline int fill_args(KArgs& a, const ort_lens* lens, const ort_batch* batch,
   // the closed-form kernels' bit alone: a lens with a Newton or interaction surface is not
   // plain whatever its flags say, and the other kernel families are selected without it
   if ((lens->frame_flags & ORT_LENS_PLAIN) && (feat & (F_KM | F_IA)) == 0) feat |= F_PLAIN;
+  // form_flags was a reserved word: honoured only when it holds the one known bit and
+  // nothing else, so a caller that never cleared it gets the plain form, not this one
+  if ((feat & F_PLAIN) != 0 && lens->form_flags == ORT_LENS_SPHERES) feat |= F_SPHERES;
   if (opt->newton_mode != ORT_NEWTON_SCHEDULE && opt->newton_mode != ORT_NEWTON_WAVE)
     return ORT_ERR_ARG;
   a.vstats = opt->verify_stats;

@@ -550,11 +550,21 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
 // within 2^-107 of (X = 1 + 2^-52 is one) only because the coupled step leaves h at its
 // own rounding, |eh| ~ 2^-53; g / 2 has 2^-50.) k != 0 and tables without the bit keep
 // v_rsq(X).
-template <bool PLAIN = false, class B>
+// SPHERES (the all-spheres form, ORT_LENS_SPHERES: PLAIN with every standard surface a
+// sphere that carries the bit): `seeded` is a constant, and a = (1 + k) r2 is r2 itself, so
+// neither s.one_plus_k nor s.flags is read. 1.0 * r2 has the bits of r2 for every r2 that
+// is not a NaN: an IEEE product with 1.0 is exact (nothing to round), zeros and infinities
+// keep their sign (sign = xor of the signs, and 1.0 is positive), and fp64 denormals are
+// not flushed on gfx950. For a NaN r2 IEEE leaves the payload to the implementation, and
+// none is claimed here: r2 is a sum, so it is a quiet NaN either way, q, g, denom and the
+// normal are NaN with or without the product, NaN is sticky in the ray state, and state_ok
+// sends the lane to the exact re-trace -- no NaN of this function is ever stored.
+template <bool PLAIN = false, bool SPHERES = false, class B>
 ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, bool sphere,
                                  double& nx, double& ny, double& nz, B& bad) {
+  static_assert(PLAIN || !SPHERES, "the all-spheres form is a plain form");
   const double r2 = x * x + y * y;
-  const double a = s.one_plus_k * r2;
+  const double a = SPHERES ? r2 : s.one_plus_k * r2;
   const double q0 = a * s.inv_r2;
   const double q = fma(fma(-s.r_sq, q0, a), s.inv_r2, q0);
   double h, g;
@@ -566,7 +576,7 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, bool 
   SharedDiv dd;
   bool seeded = false;  // the surface carries the bit
   if constexpr (PLAIN) {
-    seeded = (s.flags & ORT_SURF_TWO_INV_R) != 0;
+    seeded = SPHERES || (s.flags & ORT_SURF_TWO_INV_R) != 0;
     if (seeded)
       dd = shared_div_seeded(denom, s.norm_radius * h, bad);
     else

@@ -47,13 +47,21 @@ KernelFn select_closed(uint32_t feat) {
   // the plain form (F_PLAIN): compiled for axial lenses with generated rays, the flagship
   // trace's kernels; every other combination runs the generic form, which is right for
   // any lens
+  // the all-spheres form (F_SPHERES) is the plain form with three more uniform decisions
+  // compiled in: it exists where the plain form does and is dropped with it
   const uint32_t base = feat & (F_GEN | F_REC | F_MONO | F_WRAY | F_SPOT);
-  if ((feat & F_AXIAL) == 0 || (base != F_GEN && base != (F_GEN | F_MONO))) feat &= ~F_PLAIN;
-  switch (feat & (F_GEN | F_REC | F_MONO | F_WRAY | F_AXIAL | F_SPOT | F_PLAIN)) {
+  if ((feat & F_AXIAL) == 0 || (base != F_GEN && base != (F_GEN | F_MONO)))
+    feat &= ~(F_PLAIN | F_SPHERES);
+  if ((feat & F_PLAIN) == 0) feat &= ~F_SPHERES;
+  switch (feat & (F_GEN | F_REC | F_MONO | F_WRAY | F_AXIAL | F_SPOT | F_PLAIN | F_SPHERES)) {
     case F_GEN | F_AXIAL | F_PLAIN:
       return trace_closed_kernel<F_GEN | F_AXIAL | F_PLAIN>;
     case F_GEN | F_MONO | F_AXIAL | F_PLAIN:
       return trace_closed_kernel<F_GEN | F_MONO | F_AXIAL | F_PLAIN>;
+    case F_GEN | F_AXIAL | F_PLAIN | F_SPHERES:
+      return trace_closed_kernel<F_GEN | F_AXIAL | F_PLAIN | F_SPHERES>;
+    case F_GEN | F_MONO | F_AXIAL | F_PLAIN | F_SPHERES:
+      return trace_closed_kernel<F_GEN | F_MONO | F_AXIAL | F_PLAIN | F_SPHERES>;
 #define ORT_C(F) \
   case (F):      \
     return trace_closed_kernel<(F)>;        \

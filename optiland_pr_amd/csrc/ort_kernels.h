@@ -1102,14 +1102,15 @@ template <uint32_t FEAT>
 __device__ inline PlainSurf plain_load(const KArgs& a, int row0, int si) {
   const cptr<ort_surface> s = cst(a.surf) + si;
   PlainSurf p{};
+  constexpr bool kConic = (FEAT & F_SPHERES) == 0;  // all spheres: k = 0, 1 + k = 1, not read
   p.radius = s->radius;
-  p.conic = s->conic;
+  if constexpr (kConic) p.conic = s->conic;
   p.geometry = s->geometry;
   p.flags = s->flags;
   p.cs_tz = s->cs_t[2];
   p.inv_r2 = s->inv_r2;
   p.two_r = s->two_r;
-  p.one_plus_k = s->one_plus_k;
+  if constexpr (kConic) p.one_plus_k = s->one_plus_k;
   p.r_sq = s->r_sq;
   p.two_inv_r = s->norm_radius;
   if constexpr ((FEAT & F_MONO) != 0) {
@@ -1153,6 +1154,10 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
   constexpr bool kPlain = FAST && (FEAT & F_PLAIN) != 0;
   static_assert(!kPlain || (FEAT & (F_AXIAL | F_REC | F_WRAY)) == F_AXIAL,
                 "the plain form is the axial, unrecorded, table-wavelength kernels'");
+  // F_SPHERES beside it (ORT_LENS_SPHERES: every standard surface of the plain lens is a
+  // sphere of finite radius whose record carries ORT_SURF_TWO_INV_R): `sphere`, `seeded`
+  // and `radius_inf` are constants, so of the uniform branches only plane / sphere is left.
+  constexpr bool kSpheres = kPlain && (FEAT & F_SPHERES) != 0;
   int row0 = 0;
   if constexpr (kPlain && (FEAT & F_MONO) != 0) row0 = uniform_row(lam) * a.n_surf;
   for (int si = a.start_surface; si < a.n_surf; ++si) {
@@ -1171,7 +1176,7 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     else
       localize(a, s, r);
     const bool is_plane = s.geometry == ORT_GEOM_PLANE;
-    const bool radius_inf = (s.flags & ORT_SURF_RADIUS_INF) != 0;
+    const bool radius_inf = !kSpheres && (s.flags & ORT_SURF_RADIUS_INF) != 0;
     // FAST: this surface's range failures. A per-lane bool inside the surface (the
     // branches below are uniform, so it stays a lane mask in scalar registers) that is
     // ORed into the wave mask `bad` once, at the end of the surface: the value the loop
@@ -1179,7 +1184,8 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
     // register and back at every surface.
     bool sbad = false;
     double t;
-    const bool sphere = s.conic == 0.0;  // uniform: the quadratic's and the normal's branch
+    // uniform: the quadratic's and the normal's branch
+    const bool sphere = kSpheres || s.conic == 0.0;
     if constexpr (FAST) {
       t = is_plane ? ort::fast::distance_plane(r, sbad)
                    : ort::fast::distance_conic_folded<kPlain>(r, s, radius_inf, sphere, sbad);
@@ -1213,7 +1219,7 @@ __device__ inline void closed_surfaces(const KArgs& a, ort::Ray& r, int lam, dou
         nx = 0.0; ny = 0.0; nz = 1.0;
       } else if (kPlain || (s.flags & ORT_SURF_INV_R2)) {  // plain: every finite conic has it
         if constexpr (FAST)
-          ort::fast::normal_conic_rcp<kPlain>(r.x, r.y, s, sphere, nx, ny, nz, sbad);
+          ort::fast::normal_conic_rcp<kPlain, kSpheres>(r.x, r.y, s, sphere, nx, ny, nz, sbad);
         else
           ort::normal_conic_rcp(r.x, r.y, s.radius, s.conic, s.inv_r2, nx, ny, nz);
       } else {

@@ -55,7 +55,7 @@ class HostLens:
             addr(surfaces), addr(cs_ops), addr(coef), addr(zern), addr(n_tab), addr(alpha_tab), addr(optics),
             table.n_surfaces, len(table.wavelengths), table.n_tab.shape[1], table.final_mat,
             mask, table.interaction_mask, table.final_thickness, addr(mats), addr(lambdas),
-            table.frame_flags)
+            table.frame_flags, table.form_flags)
         self._keep = keep
         # the same nine tables as torch CPU tensors sharing these arrays' memory (the lens as
         # the torch ops take it: ops.lens_args)

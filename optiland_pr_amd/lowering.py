@@ -101,6 +101,22 @@ class LensTable:
         return (_abi.LENS_AXIAL if axial else 0) | (_abi.LENS_PLAIN if plain else 0)
 
     @property
+    def form_flags(self):
+        """ort_lens.form_flags: ORT_LENS_SPHERES when the lens is plain (ORT_LENS_PLAIN) and
+        every surface is a plane, or a standard surface with conic == 0.0 exactly, a finite
+        radius (no ORT_SURF_RADIUS_INF) and RN(2 / R) in its record (ORT_SURF_TWO_INV_R)."""
+        if not self.frame_flags & _abi.LENS_PLAIN:
+            return 0
+        s = self.surfaces
+        std = s["geometry"] == _abi.GEOM_STANDARD
+        f = s["flags"][std]
+        spheres = (np.all((s["geometry"] == _abi.GEOM_PLANE) | std)
+                   and np.all(s["conic"][std] == 0.0)
+                   and not np.any(f & _abi.SURF_RADIUS_INF)
+                   and np.all((f & _abi.SURF_TWO_INV_R) != 0))
+        return _abi.LENS_SPHERES if spheres else 0
+
+    @property
     def interaction_mask(self):
         m = 0
         for v in np.unique(self.surfaces["interaction"]):

@@ -148,7 +148,7 @@ class DeviceLens:
             self.optics.data_ptr(),
             table.n_surfaces, len(table.wavelengths), table.n_tab.shape[1], table.final_mat,
             mask, table.interaction_mask, table.final_thickness, self.mats.data_ptr(),
-            self.lambdas.data_ptr(), table.frame_flags)
+            self.lambdas.data_ptr(), table.frame_flags, table.form_flags)
         # the pupil apodization record (ort_batch.apod of generating launches)
         self.apod = None if table.apod is None else _to_device_bytes(table.apod, d)
         self.newton = table.newton_surfaces
