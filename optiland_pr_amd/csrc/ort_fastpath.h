@@ -33,8 +33,11 @@
 // is already at hand or a test cannot fire on a finite result: a sphere's norm root
 // sqrt(dfdx^2 + dfdy^2 + 1) seeded from g = sqrt(1 - q) instead of v_rsq (normal_conic_rcp,
 // sqrt_seeded_h), a sphere's 1 / (L^2 + M^2 + N^2) from 2 - a and one step
-// (shared_div_unit), and sqrt(1.0 - v) without its lower-bound test (sqrt_1m). The Newton
-// kernels' calls (template defaults) compile to what they did.
+// (shared_div_unit), and sqrt(1.0 - v) without its lower-bound test (sqrt_1m). Two more
+// drop work the stored bits do not need: a sphere's quadratic keeps the one root the
+// reference would choose, predicted by a sign and held to it by a guard
+// (distance_conic_folded), and the refraction puts the normal's alignment on one sign bit
+// (refract). The Newton kernels' calls (template defaults) compile to what they did.
 //
 // Formulas and their order follow ort_core.h (and through it the reference files cited
 // there); only the check placement differs. Host compilation: plain IEEE operations.
@@ -410,7 +413,10 @@ ORT_INLINE double distance_plane(const Ray& r, B& bad) { return div(-r.z, r.N, b
 
 // standard.py:89-140 (ort_core.h distance_conic); s.two_r = 2 R formed on the host.
 // The Newton kernels' form; distance_conic_folded below is the closed-form kernel's copy
-// with the powers of two folded out: a change here belongs there too.
+// with the powers of two folded out: a change here belongs there too -- but for that
+// copy's one-root sphere branch (plain form only), which stays out of here: these kernels
+// sit at register and scratch edges, their a is not tested to be within 2^-27 of 1 (the
+// branch's error bounds lean on it), and nothing shares z + t N with the propagation.
 ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius_inf,
                                  bool& bad) {
   if (radius_inf) {
@@ -444,6 +450,9 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
   return ::fabs(z1) <= ::fabs(zz2) ? t1 : t2;
 }
 
+// x with the sign bit of s, any x and s: one bit-field insert on the high dword
+ORT_INLINE double with_sign_of(double x, double s) { return __builtin_copysign(x, s); }
+
 // distance_conic with the powers of two folded out of the quadratic, for the closed-form
 // kernel (three multiplications and one subtraction fewer per conic); the Newton kernels
 // keep distance_conic above, and a change to either belongs in both. With
@@ -473,6 +482,56 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
 // k == 0: the reference's c starts (0.0 - 2R z) + x x. 0.0 - p is -p unless p is a zero,
 // where it is +0 and -p may be -0; x x is >= +0 or NaN, and (+-0) + (+0) = +0,
 // (+-0) + w = w: x x - p is the same value.
+//
+// PLAIN, sphere: ONE root. The reference takes both quotients t1 = (-S + sd) / a,
+// t2 = (-S - sd) / a, forms z1 = fl(z + fl(t1 N)), z2 likewise, and keeps t1 when
+// |z1| <= |z2|, else t2. Both hit points of a line with x^2 + y^2 + z^2 = 2 R z have a z
+// of R's sign, and z1 - z2 = 2 sd N / a with sd, a > 0: the hit of smaller |z| is root 1
+// exactly when N R < 0. That is only the PREDICTION (sd gets the sign bit of N xor that of
+// R, n = -S - sd_s is n1 or n2 bit for bit); what makes the kept t the reference's is the
+// guard, which proves the reference's comparison of its two ROUNDED z without forming the
+// other one. With t_c, z_c the kept root's quotient and z, t_o, z_o the other's (both as
+// the reference rounds them), u = 2^-53, and D = z_o - z_c: |z_o| >= |D| - |z_c|, so
+//   |D| > 2 |z_c|  implies  |z_c| < |z_o| strictly,
+// which selects t_c whichever root it is (root 1 wins ties, root 2 needs the strict sign),
+// and needs no fact about the signs of z_c, z_o or R. The guard is
+//   fma(-c, |z_c|, P) > 2^-300,  P = fl(sd |N|),  c = 1 + 2^-20  (a product, an fma, a compare),
+// and on a lane that raised no flag at all it implies |D| > 2 |z_c|:
+//   Size of d.  d = fl(SS - ac) >= 2^-767 (sqrt's test) is a positive difference of two
+//     doubles. For ac <= 0, d >= SS. For ac > 0, SS > ac are distinct doubles, so SS - ac is
+//     at least the spacing below SS, >= 2^-53 SS (SS >= d is normal). Either way
+//     d >= 2^-53 SS, and with SS = S S (1 + e), sd = RN(sqrt d):  |S| < 2^26.6 sd. The root
+//     cannot be arbitrarily small against |S|.
+//   Separation. n_o, n_c = fl(-S +- sd): n_o - n_c = +-2 sd + e_n, |e_n| <= 2u (|S| + sd) <
+//     2^-24.9 sd. The quotients (a within 2^-27 of 1: shared_div_unit's test) add
+//     |e_t| <= u (|n_o| + |n_c|) / a, as much again: |t_o - t_c| >= 2 sd (1 - 2^-24.6). The
+//     products fl(t N) err by u |t N| each, |t| < 2^27.2 sd: together < 2^-24.8 sd |N|.
+//     So |fl(t_o N) - fl(t_c N)| >= 2 sd |N| (1 - 2^-24): the separation is the PRODUCT
+//     2 sd |N| / a, with no cancellation in it, and every error above is relative to it.
+//   Rounding of the sums. fl(z + w) = (z + w)(1 + e), |e| <= u, is relative to the RESULT,
+//     so a |z| that is large against |S N| (a ray started far from the surface) enters
+//     only through |t N| above, already bounded by sd |N|: z_o = z_c + D gives
+//     |D| (1 + u) >= 2 sd |N| (1 - 2^-24) - 2u |z_c|.
+//   The guard.  The fma rounds P - c |z_c| once, and a rounded value above 2^-300 has a
+//     positive exact one: c |z_c| < P and P > 2^-300 is normal, P <= sd |N| (1 + u). So
+//     |z_c| < sd |N| (1 + u) / c and 2 |z_c| < 2 sd |N| (1 - 2^-20 + 2^-39) < |D|. The
+//     2^-300 keeps sd |N| out of the range where a product t N or a quotient could
+//     underflow by more than 2^-770 of it (t N is rounded on the subnormal grid to within
+//     2^-1075); every lens length the host accepts (|R| >= 2^-150) is far above it.
+//   Zero and NaN. N = +-0 makes P = 0 and the compare false (the prediction would be wrong
+//     for N = +0, R > 0: the reference's tie keeps root 1); a NaN in z_c, sd or N makes it
+//     false; d <= 0 or NaN fails sqrt's test, and d = +inf the 2^1020 test above; an
+//     infinite N passes the guard but fails |1 - a| <= 2^-27. All are flagged here, not
+//     left to state_ok.
+// The other root's |n_o| >= 2^-300 test goes with its quotient: it guarded the short
+// sequence, not the reference's value. A wrong prediction cannot store a wrong t -- its z_c
+// is the far hit, |z_c| >= |D| - |z_o| -- it only flags the lane. The guard also flags a
+// right prediction whose hit lies above half the z-extent of the chord, 3 |z_c| > |z_o|
+// (for a ray along the axis r / |R| > 0.866): correct and slow, a divergent exact re-trace.
+// The sample objectives at their bench fields flag no ray (tests/test_one_root_cpu.py).
+// k != 0, an infinite radius and the Newton kernels (distance_conic) keep both roots: a
+// conic's two hits need not lie on one side of z = 0.
+constexpr double kOneRootC = 1.0 + 0x1p-20;
 template <bool PLAIN = false, class B>
 ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool radius_inf,
                                         bool sphere, B& bad) {
@@ -498,10 +557,19 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
   const double d = SS - ac;
   const double sd = sqrt(d, bad);
   SharedDiv a1;
-  if (PLAIN && sphere)
+  if (PLAIN && sphere) {
     a1 = shared_div_unit(a, bad);
-  else
-    a1 = shared_div(a, bad);
+    // the predicted root: -S + sd (root 1) exactly when N R < 0; sd >= 0 or NaN
+    const double sd_s = with_sign_of(sd, __longlong_as_double(__double_as_longlong(r.N) ^
+                                                              __double_as_longlong(R)));
+    const double n = -S - sd_s;  // x - (-y) is x + y: n1's or n2's bits
+    ORT_CHK(bad, !num_ok(n));
+    const double t = quot_pos(n, a1);
+    const double zc = r.z + t * r.N;  // propagate's own expression: formed once
+    ORT_CHK(bad, !(fma(-kOneRootC, ::fabs(zc), ::fabs(sd_s * r.N)) > 0x1p-300));
+    return t;
+  }
+  a1 = shared_div(a, bad);
   // nonzero numerators (checked): quot_pos and quot agree for either sign of a
   const double n1 = -S + sd, n2 = -S - sd;
   ORT_CHK(bad, !(num_ok(n1) && num_ok(n2)));
@@ -624,20 +692,38 @@ ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz,
 }
 
 // rays/real_rays.py:141-163 (ort_core.h refract); u_sq = RN(u * u) from the host table
+// PLAIN (the plain form's kernels): the normal is not flipped. With s = sign(dot) = +-1
+// the aligned form above computes, per component,
+//   u L0 + (s nx) root - (u (s nx)) |dot|,        |dot| = s dot.
+// A sign flip is exact and round to nearest is sign-symmetric, RN(-p) = -RN(p), so a flip
+// of one factor moves through a rounded product: (s nx) root = nx (s root) and
+// (u (s nx)) (s dot) = s s ((u nx) dot) = (u nx) dot, bit for bit, zero products included
+// (the sign of a zero product is the xor of its factors' signs, which both sides share),
+// and a NaN on one side is a NaN on the other (never stored: state_ok). dot * dot is
+// |dot| |dot| likewise. So the raw normal, the signed dot and root_s = root with dot's sign
+// bit give the same three sums in the same order; root >= 0 or NaN (sqrt_1m), so putting
+// the bit on is the flip. dot == 0 and NaN take the exact path as before.
 template <bool PLAIN = false, class B>
 ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, double u_sq,
                         B& bad) {
-  const double dot = align_normal(r, nx, ny, nz, bad);
-  const double v = u_sq * (1.0 - dot * dot);
-  double root;
-  if constexpr (PLAIN)
-    root = sqrt_1m(1.0 - v);
-  else
-    root = sqrt(1.0 - v, bad);
-  const double L0 = r.L, M0 = r.M, N0 = r.N;
-  r.L = u * L0 + nx * root - u * nx * dot;
-  r.M = u * M0 + ny * root - u * ny * dot;
-  r.N = u * N0 + nz * root - u * nz * dot;
+  if constexpr (PLAIN) {
+    const double dot = r.L * nx + r.M * ny + r.N * nz;
+    ORT_CHK(bad, !(::fabs(dot) > 0.0));
+    const double v = u_sq * (1.0 - dot * dot);
+    const double root_s = with_sign_of(sqrt_1m(1.0 - v), dot);
+    const double L0 = r.L, M0 = r.M, N0 = r.N;
+    r.L = u * L0 + nx * root_s - u * nx * dot;
+    r.M = u * M0 + ny * root_s - u * ny * dot;
+    r.N = u * N0 + nz * root_s - u * nz * dot;
+  } else {
+    const double dot = align_normal(r, nx, ny, nz, bad);
+    const double v = u_sq * (1.0 - dot * dot);
+    const double root = sqrt(1.0 - v, bad);
+    const double L0 = r.L, M0 = r.M, N0 = r.N;
+    r.L = u * L0 + nx * root - u * nx * dot;
+    r.M = u * M0 + ny * root - u * ny * dot;
+    r.N = u * N0 + nz * root - u * nz * dot;
+  }
 }
 
 // Refraction at a flat surface: the plane normal (0, 0, 1) (plane.py:79-98) or the

@@ -1,0 +1,332 @@
+"""The plain closed-form kernel's one-root sphere quadratic and its single sign flip per
+refraction (ort_fastpath.h distance_conic_folded<PLAIN>'s sphere branch, refract<PLAIN>),
+restated operation for operation in NumPy beside the reference's two-root sequence
+(oracle/trace_np.distance_conic). No GPU.
+
+The fast pass's square root and quotients are the IEEE operations on every lane that raises
+no flag (test_seed_sequences_cpu.py, test_sphere_norm_seed_cpu.py), so they are NumPy's
+here; the guard's fma is evaluated exactly (fractions.Fraction) wherever a double estimate
+is within a few ulps of its threshold. What is asserted, over every operand set: a lane on
+which the branch raises no flag returns the reference's t bit for bit.
+"""
+
+import numpy as np
+import pytest
+
+from oracle import trace_np
+from tests.test_seed_sequences_cpu import fma
+
+C_GUARD = 1.0 + 2.0**-20  # kOneRootC
+T_GUARD = 2.0**-300
+
+
+def _bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _guard_flag(zc, P):
+    """ORT_CHK(bad, !(fma(-c, |zc|, |P|) > 2^-300)), elementwise."""
+    az, ap = np.abs(zc), np.abs(P)
+    with np.errstate(all="ignore"):
+        est = (ap - az) - az * 2.0**-20
+        tol = 4.0 * np.spacing(np.maximum(ap, az)) + 2.0**-1060
+        flag = ~(est > T_GUARD + tol)
+        unsure = np.isfinite(az) & np.isfinite(ap) & ~(est > T_GUARD + tol) & ~(est < T_GUARD - tol)
+    for i in np.flatnonzero(unsure):
+        flag[i] = not fma(-C_GUARD, float(az[i]), float(ap[i])) > T_GUARD
+    inf_p = np.isinf(ap) & np.isfinite(az)  # fma(-c, finite, inf) = inf: passes
+    flag[inf_p] = False
+    return flag
+
+
+def one_root(x, y, z, L, M, N, R):
+    """-> (t, flagged, guard alone): the sphere branch of distance_conic_folded<true>."""
+    with np.errstate(all="ignore"):
+        a = L * L + M * M + N * N
+        S = L * x + M * y - N * R + N * z
+        c = x * x - (2.0 * R) * z + y * y + z * z
+        SS, ac = S * S, a * c
+        flag = ~((SS < 2.0**1020) & (np.abs(ac) < 2.0**1020))
+        d = SS - ac
+        sd = np.sqrt(d)
+        flag |= ~(d >= 2.0**-767)
+        flag |= ~(np.abs(1.0 - a) <= 2.0**-27)
+        sd_s = np.copysign(sd, np.where(np.signbit(N) ^ np.signbit(R), -1.0, 1.0))
+        n = -S - sd_s
+        flag |= ~(np.abs(n) >= 2.0**-300)
+        t = n / a
+        zc = z + t * N
+        guard = _guard_flag(zc, sd_s * N)
+        # the proof's "size of d": a root that passed sqrt's test is not far below |S|
+        ok = d >= 2.0**-767
+        assert np.all(d[ok] >= 2.0**-53 * SS[ok])
+    return t, flag | guard, guard
+
+
+def _reference(x, y, z, L, M, N, R):
+    r = trace_np.Rays(x.copy(), y.copy(), z.copy(), L.copy(), M.copy(), N.copy(), np.ones_like(x))
+    with np.errstate(all="ignore"):
+        return trace_np.distance_conic(r, float(R), 0.0, False)
+
+
+def _check(x, y, z, L, M, N, R, what):
+    """-> the share of unflagged lanes, after asserting that each returns the reference's t."""
+    arrs = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), np.shape(x)))
+            for v in (x, y, z, L, M, N)]
+    t, flagged, guard = one_root(*arrs, float(R))
+    ref = _reference(*arrs, float(R))
+    keep = ~flagged
+    assert np.all(np.isfinite(t[keep])), what
+    bad = keep & (_bits(t) != _bits(ref))
+    assert not bad.any(), (what, R, [a[bad][:3] for a in arrs], t[bad][:3], ref[bad][:3])
+    return keep.mean(), guard.mean()
+
+
+def _unit(rng, n, nz_lo=0.05, nz_hi=1.0):
+    """Unit directions rounded to doubles, |N| in [nz_lo, nz_hi], N of both signs."""
+    N = rng.uniform(nz_lo, nz_hi, n) * rng.choice([-1.0, 1.0], n)
+    th = rng.uniform(0, 2 * np.pi, n)
+    s = np.sqrt(1.0 - N * N)
+    return s * np.cos(th), s * np.sin(th), N
+
+
+def _near_hit(rng, n, R, rho_lo, rho_hi):
+    """Points of the sphere x^2 + y^2 + z^2 = 2 R z on the vertex's side, r / |R| in range."""
+    rho = rng.uniform(rho_lo, rho_hi, n)
+    th = rng.uniform(0, 2 * np.pi, n)
+    return abs(R) * rho * np.cos(th), abs(R) * rho * np.sin(th), R * (1.0 - np.sqrt(1.0 - rho * rho))
+
+
+RADII = [22.01359, -435.76044, 1.0, -3.0, 2.0**140 * 1.37, -(2.0**-140) * 1.91]
+
+
+@pytest.mark.parametrize("R", RADII)
+def test_random_rays(R):
+    rng = np.random.default_rng(21)
+    n = 4000
+    hx, hy, hz = _near_hit(rng, n, R, 0.0, 0.6)
+    L, M, N = _unit(rng, n, 0.3)
+    s = rng.uniform(-2.0, 2.0, n) * abs(R)  # starts before and behind the hit
+    kept, _ = _check(hx - s * L, hy - s * M, hz - s * N, L, M, N, R, "random")
+    assert kept > 0.5  # ordinary rays are not flagged
+    # the far hit as the start's neighbour, and rays that miss
+    L, M, N = _unit(rng, n)
+    _check(rng.normal(0, abs(R), n), rng.normal(0, abs(R), n), rng.normal(0, 2 * abs(R), n),
+           L, M, N, R, "anywhere")
+
+
+@pytest.mark.parametrize("R", [22.01359, -435.76044])
+def test_far_starts(R):
+    """z from R to 2^40 R before the surface, N down to 2^-20: the rounding of z + t N is
+    then as large as the z-extent of the chord, and the reference's comparison is decided by
+    it. The guard has to flag such lanes (and does flag some), never return another t."""
+    rng = np.random.default_rng(22)
+    n = 600
+    flagged_any, kept_any = 0.0, 0.0
+    for e in (0, 10, 20, 30, 40):
+        for nz in (1.0, 0.5, 2.0**-5, 2.0**-10, 2.0**-20):
+            hx, hy, hz = _near_hit(rng, n, R, 0.0, 0.5)
+            L, M, N = _unit(rng, n, nz * 0.999 if nz < 1.0 else 0.9, nz)
+            s = 2.0**e * abs(R) / np.abs(N) * rng.uniform(1.0, 2.0, n)
+            kept, guard = _check(hx - s * L, hy - s * M, hz - s * N, L, M, N, R, f"far 2^{e} N={nz}")
+            flagged_any, kept_any = max(flagged_any, guard), max(kept_any, kept)
+    assert flagged_any > 0.0 and kept_any > 0.5
+
+
+@pytest.mark.parametrize("R", [22.01359, -3.0])
+def test_near_tangent(R):
+    """The last lateral offsets at which d = SS - ac is still positive, and the first at
+    which it rounds to 0 or below."""
+    rng = np.random.default_rng(23)
+    cases = []
+    for _ in range(40):
+        L, M, N = (float(v[0]) for v in _unit(rng, 1, 0.2))
+        z0 = float(rng.uniform(-3.0, 3.0)) * abs(R)
+
+        def d_of(x0):
+            a = L * L + M * M + N * N
+            S = L * x0 - N * R + N * z0
+            c = x0 * x0 - (2.0 * R) * z0 + z0 * z0
+            return S * S - a * c
+
+        lo, hi = 0.0, 16.0 * abs(R)
+        if not (d_of(lo) > 0.0 and d_of(hi) <= 0.0):
+            continue
+        for _ in range(80):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if d_of(mid) > 0.0 else (lo, mid)
+        x0 = lo
+        for _ in range(12):
+            x0 = float(np.nextafter(x0, 0.0))
+        for _ in range(24):
+            cases.append((x0, 0.0, z0, L, M, N))
+            x0 = float(np.nextafter(x0, np.inf))
+    assert len(cases) > 200
+    x, y, z, L, M, N = (np.array(v) for v in zip(*cases))
+    # M is not zero: the plane of the ray is not y = 0, but y0 = 0 keeps d_of the whole d
+    _check(x, y, z, L, M, N, R, "tangent")
+    with np.errstate(all="ignore"):
+        a = L * L + M * M + N * N
+        S = L * x + M * y - N * R + N * z
+        d = S * S - a * (x * x - (2.0 * R) * z + y * y + z * z)
+    assert np.any(d > 0.0) and np.any(d <= 0.0)
+
+
+@pytest.mark.parametrize("R", RADII)
+def test_vertex_hits(R):
+    """Rays aimed at the vertex from points formed in floating point: z_c lands within a
+    few ulps of 0 on either side."""
+    rng = np.random.default_rng(24)
+    n = 3000
+    L, M, N = _unit(rng, n, 0.2)
+    s = rng.uniform(0.1, 4.0, n) * abs(R) * rng.choice([-1.0, 1.0], n)
+    x, y, z = -s * L, -s * M, -s * N
+    kept, _ = _check(x, y, z, L, M, N, R, "vertex")
+    assert kept > 0.9
+    t, _, _ = one_root(x, y, z, L, M, N, float(R))
+    zc = z + t * N
+    assert np.any(zc > 0.0) and np.any(zc < 0.0) and np.any(zc == 0.0)
+    assert np.all(np.abs(zc) <= 2.0**-45 * abs(R))
+
+
+@pytest.mark.parametrize("R", [22.01359, -3.0])
+def test_hemispherical_hits(R):
+    rng = np.random.default_rng(25)
+    n = 3000
+    hx, hy, hz = _near_hit(rng, n, R, 0.7, 1.0)
+    for nz_lo in (0.999, 0.5):
+        L, M, N = _unit(rng, n, nz_lo)
+        s = rng.uniform(0.5, 3.0, n) * abs(R)
+        kept, guard = _check(hx - s * L, hy - s * M, hz - s * N, L, M, N, R, "hemisphere")
+        assert 0.0 < guard  # hits above half the chord's z-extent are flagged ...
+        assert kept > 0.0  # ... the others are not
+
+
+def test_zero_nan_and_infinite_operands():
+    R = 22.01359
+    inf, nan = np.inf, np.nan
+    specials = [0.0, -0.0, nan, inf, -inf, 2.0**-1074, 2.0**600, -(2.0**600)]
+    rows = []
+    for v in specials:
+        rows += [(1.0, 2.0, -5.0, 0.6, 0.0, v), (1.0, 2.0, -5.0, 0.0, 1.0, v),  # N
+                 (v, 2.0, -5.0, 0.0, 0.6, 0.8), (1.0, 2.0, v, 0.0, 0.6, 0.8),  # x, z
+                 (1.0, 2.0, -5.0, v, 0.6, 0.8), (v, v, v, 0.0, 0.6, 0.8)]
+    x, y, z, L, M, N = (np.array(c, dtype=np.float64) for c in zip(*rows))
+    for Rs in (R, -R):
+        _check(x, y, z, L, M, N, Rs, "specials")
+        # N = +-0: whatever its sign bit predicts, the lane is flagged (the reference's tie)
+        zero_n = N == 0.0
+        _, flagged, _ = one_root(x, y, z, L, M, N, Rs)
+        assert flagged[zero_n].all() and flagged[~np.isfinite(N)].all()
+
+
+# ---- the bench lenses ---------------------------------------------------------------------
+
+N_PREFIX = 65536
+
+
+def _random_prefix(seed, n_full, m=N_PREFIX):
+    """The first m points of RandomDistribution(seed).generate_points(n_full): r from the
+    stream's start, theta from n_full draws on."""
+    r = np.random.default_rng(seed).uniform(size=m)
+    g = np.random.default_rng(seed)
+    g.bit_generator.advance(n_full)
+    theta = g.uniform(0, 2 * np.pi, size=m)
+    return np.sqrt(r) * np.cos(theta), np.sqrt(r) * np.sin(theta)
+
+
+def test_random_prefix_is_the_distribution_s():
+    from optiland_pr_amd.distribution import RandomDistribution
+
+    d = RandomDistribution(seed=3)
+    d.generate_points(200_000)
+    px, py = _random_prefix(3, 200_000, 1000)
+    np.testing.assert_array_equal(px, d.x[:1000])
+    np.testing.assert_array_equal(py, d.y[:1000])
+
+
+def _bench_workloads():
+    """(name, lens, wavelengths, [(Hy, lambda_idx, px, py)]) of bench.py's configs 1, 2, 4."""
+    from optiland_pr_amd import samples
+    from optiland_pr_amd.distribution import UniformDistribution
+
+    d = UniformDistribution()
+    d.generate_points(128)
+    ux, uy = np.ascontiguousarray(d.x), np.ascontiguousarray(d.y)
+    yield "config1", samples.CookeTriplet(), [0.55], [(h, 0, ux, uy) for h in (0.0, 0.7, 1.0)]
+    yield "config2", samples.DoubleGauss(), [0.5876], [(1.0, 0, *_random_prefix(0, 1_000_000))]
+    wls = [float(w) for w in np.linspace(0.4861, 0.6563, 7)]
+    pairs = [(float(h), wi) for h in np.linspace(0, 1, 7) for wi in range(7)]
+    yield "config4", samples.ReverseTelephoto(), wls, [
+        (h, wi, *_random_prefix(k, 2_000_000)) for k, (h, wi) in enumerate(pairs)]
+
+
+def test_bench_lenses_flag_no_ray(monkeypatch):
+    """bench.py's rays of configs 1, 2 and 4 (a 65,536-ray prefix per pair) through the
+    oracle, the branch evaluated on the operands of every sphere: no flag at all, and the
+    reference's t."""
+    from optiland_pr_amd.lowering import lower_surface_group, segment_params
+
+    seen = {"spheres": 0, "rays": 0, "flagged": 0}
+    inner = trace_np.distance_conic
+
+    def spy(r, R, k, radius_inf):
+        ref = inner(r, R, k, radius_inf)
+        if k == 0.0 and not radius_inf:
+            t, flagged, _ = one_root(r.x, r.y, r.z, r.L, r.M, r.N, float(R))
+            seen["spheres"] += 1
+            seen["rays"] += t.size
+            seen["flagged"] += int(flagged.sum())
+            keep = ~flagged
+            assert np.array_equal(_bits(t)[keep], _bits(ref)[keep])
+        return ref
+
+    monkeypatch.setattr(trace_np, "distance_conic", spy)
+    for name, lens, wls, pairs in _bench_workloads():
+        table = lower_surface_group(lens.surface_group, wls)
+        kw = {}
+        if name == "config4":
+            kw = dict(EPL=lens.paraxial.EPL(), EPD=lens.paraxial.EPD())
+        before = seen["spheres"]
+        for hy, wi, px, py in pairs:
+            seg = segment_params(lens, 0.0, hy, wi, **kw)
+            with np.errstate(all="ignore"):
+                trace_np.trace_segment(table, trace_np.generate_rays(seg, px, py), wi)
+        assert seen["spheres"] > before, name
+    assert seen["rays"] > 49 * N_PREFIX and seen["flagged"] == 0, seen
+
+
+# ---- refract<PLAIN>: one sign flip ----------------------------------------------------------
+
+def test_sign_folded_into_the_root():
+    """u L0 + nx root_s - (u nx) dot with root_s = copysign(root, dot) against the aligned
+    normal's u L0 + (s nx) root - (u (s nx)) |dot|, s = sign(dot): the same bits, zero
+    components of the normal and exactly cancelling sums included."""
+    rng = np.random.default_rng(26)
+    n = 20000
+    u = rng.uniform(0.5, 2.0, n)
+    L0 = rng.uniform(-1.0, 1.0, n)
+    nx = rng.uniform(-1.0, 1.0, n)
+    root = rng.uniform(0.0, 1.0, n)
+    dot = rng.uniform(-1.0, 1.0, n)
+    # small dyadic operands: sums that cancel to a zero whose sign has to agree
+    m = n // 4
+    u[:m] = rng.choice([0.5, 1.0, 1.5, 2.0], m)
+    L0[:m] = rng.integers(-4, 5, m) / 4.0
+    nx[:m] = rng.integers(-4, 5, m) / 4.0
+    root[:m] = rng.integers(0, 5, m) / 4.0
+    dot[:m] = rng.choice([-1.0, -0.5, -0.25, 0.25, 0.5, 1.0], m)
+    nx[m:m + 50] = 0.0
+    nx[m + 50:m + 100] = -0.0
+    L0[m + 25:m + 75] = rng.choice([0.0, -0.0], 50)
+    assert np.all(dot != 0.0) and np.any(dot < 0.0) and np.any(dot > 0.0)
+    s = np.sign(dot)
+    nxs = nx * s
+    aligned = u * L0 + nxs * root - u * nxs * np.abs(dot)
+    folded = u * L0 + nx * np.copysign(root, dot) - u * nx * dot
+    assert np.array_equal(_bits(aligned), _bits(folded))
+    assert np.any((aligned == 0.0) & np.signbit(aligned)) or np.any(aligned == 0.0)
+    # the flip is the sign-bit xor the kernel's align_normal makes
+    assert np.array_equal(_bits(nxs), _bits(nx) ^ (_bits(dot) & np.uint64(1 << 63)))
+    # and dot * dot is |dot| |dot|
+    assert np.array_equal(_bits(dot * dot), _bits(np.abs(dot) * np.abs(dot)))
