@@ -107,6 +107,13 @@ int ort_host_irradiance_bin_vjp(const double* x, const double* y, const double* 
                                 const double* grad_out, double* grad_x, double* grad_y,
                                 double* grad_power);
 
+/* ort_dft_psf on host memory (added within v3): the kernels' own terms (csrc/ort_dft.h) in
+ * the kernels' order -- T = g R summed over k, then |R^T T|^2 summed over j, each from zero in
+ * index order -- OpenMP over the rows (the value does not depend on the thread count). Same
+ * argument checks as ort_dft_psf, no workspace. */
+int ort_host_dft_psf(const double* amp, const double* opd_waves, int64_t batch, int64_t n,
+                     int64_t m, double pad, double* out);
+
 /* ort_trace_pupil_polarized / ort_trace_sequential_polarized on host memory (added within
  * v3): the kernels' per-ray polarization code (csrc/ort_polar.h) inside the host trace, so
  * the ray geometry is ort_host_trace_pupil's / ort_host_trace_sequential's bit for bit.

@@ -1001,6 +1001,38 @@ int ort_irradiance_bin_vjp(const double* x, const double* y, const double* power
                            double pixel_area, const double* grad_out, double* grad_x,
                            double* grad_y, double* grad_power, void* stream);
 
+/* ---- FFT / MMDFT PSF (psf/fft.py:169-234, psf/mmdft.py:164-184, 230-290; added within
+ * v21: new entry point only) ------------------------------------------------------------
+ * The pupil-to-image transform of FFTPSF, MMDFTPSF and FFTMTF as one fused fp64 DFT. For each
+ * of `batch` pupils (amp[n][n], opd_waves[n][n], row-major, row index j, column index k):
+ *   g[j,k]   = amp[j,k] exp(-2 pi i opd_waves[j,k])
+ *   out[v,u] = |sum_j sum_k g[j,k] exp(-2 pi i ((v - m/2)(j - n/2) + (u - m/2)(k - n/2)) / pad)|^2
+ * for v, u in [0, m) (integer divisions). MMDFTPSF's L g R is this with its pad_size; FFTPSF's
+ * fftshift(fft2(zero-padded pupil)) is it with pad = m = grid_size (the padding offset and
+ * the shift change each output by a unit-modulus factor only). Phases are reduced in cycles
+ * in fp64 before the sincos (csrc/ort_dft.h); the complex pupil and the twiddle matrices are
+ * never stored. Two launches: T = g R ([batch][n][m] complex, in the workspace), summed over
+ * k from zero in index order, then out = |R^T T|^2 summed over j likewise: no atomics, no
+ * cross-lane sums, so a value depends on nothing but its pupil, n, m and pad (not on the batch
+ * position, the grid or the stream).
+ *
+ * The kernels' tile edges: stage B's workgroup covers 8 rows v and two columns u per thread,
+ * ORT_DFT_TILE_M apart (stage A's tiles are 64 columns of u); both stages sum in chunks of
+ * ORT_DFT_TILE_K (stage A's tiles are that many rows j as well). n, m <= ORT_DFT_MAX_SIZE. */
+#define ORT_DFT_TILE_M 256
+#define ORT_DFT_TILE_K 32
+#define ORT_DFT_MAX_SIZE 32768
+
+/* Bytes of device workspace ort_dft_psf needs (< 0: ORT_ERR_ARG). */
+int64_t ort_dft_workspace_size(int64_t batch, int64_t n, int64_t m);
+
+/* amp, opd_waves: [batch][n][n] device doubles; out: [batch][m][m]. batch == 0 or m == 0
+ * launches nothing. ORT_ERR_ARG for a negative batch or m, n < 1, a size above
+ * ORT_DFT_MAX_SIZE, pad <= 0 or not finite, null pointers of a positive count or a short
+ * workspace. Two launches on `stream`, no synchronisation. */
+int ort_dft_psf(const double* amp, const double* opd_waves, int64_t batch, int64_t n, int64_t m,
+                double pad, double* out, void* workspace, int64_t workspace_size, void* stream);
+
 /* Ray generation only (ray_generator.py:28-106): fills rays_out from pupil points. */
 int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,
                       const ort_batch* batch, void* stream);

@@ -8,13 +8,15 @@ SurfaceGroup / RealRays / SpotDiagram / Wavefront interface.
 
 from . import _abi
 from . import ops  # noqa: F401  (registers torch.ops.ort.trace_sequential / trace_pupil / huygens_psf /
-# irradiance_bin)
+# dft_psf / irradiance_bin)
 from .distribution import create_distribution
 from .irradiance import IncoherentIrradiance
 from .materials import IdealMaterial, Material
+from .mtf import FFTMTF
 from .optic import Optic
-from .psf import HuygensPSF
+from .psf import FFTPSF, MMDFTPSF, HuygensPSF
 
-__all__ = ["Optic", "IdealMaterial", "Material", "HuygensPSF", "IncoherentIrradiance",
+__all__ = ["Optic", "IdealMaterial", "Material", "HuygensPSF", "FFTPSF", "MMDFTPSF", "FFTMTF",
+           "IncoherentIrradiance",
            "create_distribution", "_abi"]
 __version__ = "0.1.0"

@@ -214,6 +214,8 @@ DEVICE_PROTOTYPES = {
     "ort_huygens_workspace_size": (I64, [I64, I64]),
     "ort_huygens_psf": (C.c_int, [PTR, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR, I64, F64, F64,
                                   PTR, PTR, I64, PTR]),
+    "ort_dft_workspace_size": (I64, [I64, I64, I64]),
+    "ort_dft_psf": (C.c_int, [PTR, PTR, I64, I64, I64, F64, PTR, PTR, I64, PTR]),
     "ort_irradiance_workspace_size": (I64, [I64, I64]),
     "ort_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64, PTR, PTR,
                                      I64, PTR]),
@@ -243,6 +245,7 @@ HOST_PROTOTYPES = {
     "ort_host_set_threads": (None, [I32]),
     "ort_host_huygens_psf": (C.c_int, [PTR, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR, I64, F64,
                                        F64, PTR]),
+    "ort_host_dft_psf": (C.c_int, [PTR, PTR, I64, I64, I64, F64, PTR]),
     "ort_host_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64,
                                           PTR]),
     "ort_host_irradiance_bin_vjp": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, F64, PTR,

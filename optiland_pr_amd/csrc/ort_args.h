@@ -314,6 +314,19 @@ inline int fill_args(KArgs& a, const ort_lens* lens, const ort_batch* batch,
   return ORT_OK;
 }
 
+// ort_dft_psf / ort_host_dft_psf: the checks both libraries make (the device adds its
+// workspace and grid limits).
+inline int dft_check(const double* amp, const double* opd, int64_t batch, int64_t n, int64_t m,
+                     double pad, const double* out) {
+  if (batch < 0 || n < 1 || m < 0 || n > ORT_DFT_MAX_SIZE || m > ORT_DFT_MAX_SIZE)
+    return ORT_ERR_ARG;
+  if (!(pad > 0.0) || !(pad <= 1.79769313486231570815e308)) return ORT_ERR_ARG;
+  if (batch > 0 && (!amp || !opd)) return ORT_ERR_ARG;
+  if (batch > 0 && m > 0 && !out) return ORT_ERR_ARG;
+  if (batch > INT64_MAX / 16 / ORT_DFT_MAX_SIZE / ORT_DFT_MAX_SIZE) return ORT_ERR_ARG;
+  return ORT_OK;
+}
+
 // Table lookup n_tab[lam][mat]: a uniform scalar load when the lens is traced at one
 // wavelength (the common case), else a per-lane load of the small L1-resident table.
 ORT_INLINE double tab(const double* t, int n_lambda, int n_mat, int lam, int mat) {

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "ort_dft.h"
 #include "ort_huygens.h"
 #include "ort_irradiance.h"
 #include "ort_sweep.h"
@@ -662,6 +663,53 @@ int ort_host_huygens_psf(const double* ix, const double* iy, const double* iz, i
       j0 = j1;
     } while (j0 < n_pupil);
     psf[p] = re * re + im * im;
+  }
+  return ORT_OK;
+}
+
+// The FFT / MMDFT PSF transform (psf/mmdft.py:164-184, psf/fft.py:169-234) on host memory:
+// the kernels' terms and their order of additions (ort_dft.h, ort_k_dft.hip). Per pupil the
+// complex pupil g and the twiddles W(u - m/2, k - n/2) are formed once (the twiddles of stage
+// B are the same family: W is symmetric in its arguments), then T = g R row by row and
+// |R^T T|^2 row by row over OpenMP threads.
+int ort_host_dft_psf(const double* amp, const double* opd_waves, int64_t batch, int64_t n,
+                     int64_t m, double pad, double* out) {
+  const int rc = dft_check(amp, opd_waves, batch, n, m, pad, out);
+  if (rc != ORT_OK) return rc;
+  if (batch == 0 || m == 0) return ORT_OK;
+  const int64_t ipad = ort::dft_int_pad(pad), hn = n / 2, hm = m / 2;
+  const int nt = threads_for(n * m * (n + m));
+  std::vector<double> w(2 * m * n), g(2 * n * n), t(2 * n * m);  // W[u][k], g[j][k], T[j][u]
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int64_t u = 0; u < m; ++u)
+    for (int64_t k = 0; k < n; ++k)
+      ort::dft_twiddle(u - hm, k - hn, pad, ipad, w[2 * (u * n + k)], w[2 * (u * n + k) + 1]);
+  for (int64_t b = 0; b < batch; ++b) {
+    const double* am = amp + b * n * n;
+    const double* op = opd_waves + b * n * n;
+    double* o = out + b * m * m;
+#pragma omp parallel for num_threads(nt) schedule(static)
+    for (int64_t j = 0; j < n; ++j) {
+      for (int64_t k = 0; k < n; ++k)
+        ort::dft_pupil(am[j * n + k], op[j * n + k], g[2 * (j * n + k)], g[2 * (j * n + k) + 1]);
+      for (int64_t u = 0; u < m; ++u) {
+        double sr = 0.0, si = 0.0;
+        for (int64_t k = 0; k < n; ++k)
+          ort::dft_mac(g[2 * (j * n + k)], g[2 * (j * n + k) + 1], w[2 * (u * n + k)],
+                       w[2 * (u * n + k) + 1], sr, si);
+        t[2 * (j * m + u)] = sr;
+        t[2 * (j * m + u) + 1] = si;
+      }
+    }
+#pragma omp parallel for num_threads(nt) schedule(static)
+    for (int64_t v = 0; v < m; ++v)
+      for (int64_t u = 0; u < m; ++u) {
+        double sr = 0.0, si = 0.0;
+        for (int64_t j = 0; j < n; ++j)
+          ort::dft_mac(w[2 * (v * n + j)], w[2 * (v * n + j) + 1], t[2 * (j * m + u)],
+                       t[2 * (j * m + u) + 1], sr, si);
+        o[v * m + u] = sr * sr + si * si;
+      }
   }
   return ORT_OK;
 }

@@ -242,6 +242,16 @@ def huygens_psf(image, pupil, wavelength_mm, rp):
     return psf
 
 
+def dft_psf(amp, opd_waves, batch, n, m, pad):
+    """ort_host_dft_psf: the raw |field|^2 [batch * m * m] of contiguous float64 CPU tensors
+    amp, opd_waves [batch * n * n]."""
+    lib = _native.load_host()
+    out = torch.empty(batch * m * m, dtype=torch.float64)
+    rc = lib.ort_host_dft_psf(addr(amp), addr(opd_waves), batch, n, m, float(pad), addr(out))
+    _native.check(rc, "ort_host_dft_psf")
+    return out
+
+
 def irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=0.0):
     """ort_host_irradiance_bin: the flat map [nx * ny] of contiguous float64 CPU tensors
     (histogram: index ix * ny + iy; bilinear: iy * nx + ix)."""

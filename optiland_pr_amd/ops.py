@@ -44,6 +44,10 @@ wavelength_mm, rp) -> psf is HuygensPSF's summation (psf/huygens_fresnel_strateg
 ort_huygens_psf) on both keys; it has no autograd formula yet and refuses inputs that require
 grad.
 
+ort::dft_psf(amp, opd_waves, image_size, pad_size) -> psf is the pupil-to-image transform of
+FFTPSF, MMDFTPSF and FFTMTF (psf/fft.py:169-234, psf/mmdft.py:164-184, ort_dft_psf) on both
+keys, of one (n, n) pupil or a batch (B, n, n); it refuses inputs that require grad.
+
 ort::irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=None) -> map is
 IncoherentIrradiance's binning (analysis/irradiance.py:243-330, ort_irradiance_bin) on both
 keys: mode _abi.BIN_HISTOGRAM ([nx, ny], numpy.histogram2d's pixels) or _abi.BIN_BILINEAR
@@ -1011,6 +1015,95 @@ def _huygens_backward(ctx, grad):
 
 
 huygens_psf.register_autograd(_huygens_backward, setup_context=_huygens_setup)
+
+
+# --------------------------------------------------------------------------------------
+# ort::dft_psf -- the pupil-to-image transform of FFTPSF / MMDFTPSF / FFTMTF
+# (psf/fft.py:169-234, psf/mmdft.py:164-184, 230-290)
+# --------------------------------------------------------------------------------------
+def _check_dft_inputs(amp, opd_waves, image_size, pad_size):
+    """Two float64 contiguous tensors of one shape (n, n) or (B, n, n) on one device;
+    -> (B, n, batched)."""
+    for t in (amp, opd_waves):
+        if t.dtype != torch.float64:
+            raise ValueError(f"ort::dft_psf: every tensor must be float64 (got {t.dtype})")
+        if not t.is_contiguous():
+            raise ValueError("ort::dft_psf: amp and opd_waves must be contiguous")
+    if amp.device != opd_waves.device:
+        raise ValueError(f"ort::dft_psf: tensors on {amp.device} and {opd_waves.device}")
+    if amp.shape != opd_waves.shape or amp.dim() not in (2, 3) or amp.shape[-1] != amp.shape[-2]:
+        raise ValueError("ort::dft_psf: amp and opd_waves must both be (n, n) or (B, n, n) "
+                         f"(got {tuple(amp.shape)} and {tuple(opd_waves.shape)})")
+    n = int(amp.shape[-1])
+    if n == 0:
+        raise ValueError("ort::dft_psf: the pupil grid is empty (n == 0)")
+    if not pad_size > 0.0 or pad_size == float("inf"):
+        raise ValueError(f"ort::dft_psf: pad_size must be positive and finite (got {pad_size})")
+    if image_size < 0 or max(n, image_size) > _abi.DFT_MAX_SIZE:
+        raise ValueError(f"ort::dft_psf: n and image_size must lie in [0, {_abi.DFT_MAX_SIZE}] "
+                         f"(got {n} and {image_size})")
+    return (int(amp.shape[0]) if amp.dim() == 3 else 1), n, amp.dim() == 3
+
+
+def _dft_shape(batch, batched, m):
+    return (batch, m, m) if batched else (m, m)
+
+
+@torch.library.custom_op("ort::dft_psf", mutates_args=(), device_types="cuda")
+def dft_psf(amp: torch.Tensor, opd_waves: torch.Tensor, image_size: int,
+            pad_size: float) -> torch.Tensor:
+    """ort_dft_psf on the current stream: |sum_jk amp exp(-2 pi i opd_waves) exp(-2 pi i ((v -
+    m/2)(j - n/2) + (u - m/2)(k - n/2)) / pad_size)|^2 for v, u in [0, image_size) -- the raw
+    image intensity of FFTPSF (pad_size = image_size = grid_size) and MMDFTPSF, of one (n, n)
+    pupil or a batch (B, n, n) in one pair of launches; no host synchronisation. Not
+    differentiable: a requires_grad input raises NotImplementedError."""
+    from .raytrace import _stream_handle
+
+    lib = _native.load()
+    batch, n, batched = _check_dft_inputs(amp, opd_waves, image_size, pad_size)
+    m = int(image_size)
+    out = torch.empty(_dft_shape(batch, batched, m), dtype=torch.float64, device=amp.device)
+    size = int(lib.ort_dft_workspace_size(batch, n, m))
+    _native.check(size if size < 0 else 0, "ort_dft_workspace_size")
+    ws = torch.empty(max(size, 8), dtype=torch.uint8, device=amp.device)
+    rc = lib.ort_dft_psf(addr(amp.detach()), addr(opd_waves.detach()), batch, n, m,
+                         float(pad_size), addr(out), addr(ws), size, _stream_handle())
+    _native.check(rc, "ort_dft_psf")
+    return out
+
+
+@dft_psf.register_kernel("cpu")
+def _dft_psf_cpu(amp, opd_waves, image_size, pad_size):
+    """The CPU dispatch key: the same terms and summation order in the host library."""
+    from . import host
+
+    batch, n, batched = _check_dft_inputs(amp, opd_waves, image_size, pad_size)
+    m = int(image_size)
+    out = host.dft_psf(amp.detach(), opd_waves.detach(), batch, n, m, pad_size)
+    return out.reshape(_dft_shape(batch, batched, m))
+
+
+@dft_psf.register_fake
+def _(amp, opd_waves, image_size, pad_size):
+    batch, _, batched = _check_dft_inputs(amp, opd_waves, image_size, pad_size)
+    return amp.new_empty(_dft_shape(batch, batched, int(image_size)), dtype=torch.float64)
+
+
+_DFT_NO_GRAD = ("ort::dft_psf is not differentiable: autograd through the FFT / MMDFT PSF is "
+                "not implemented (detach the inputs)")
+
+
+def _dft_setup(ctx, inputs, output):
+    # refuse in the forward, as ort::huygens_psf does
+    if any(ctx.needs_input_grad):
+        raise NotImplementedError(_DFT_NO_GRAD)
+
+
+def _dft_backward(ctx, grad):
+    raise NotImplementedError(_DFT_NO_GRAD)
+
+
+dft_psf.register_autograd(_dft_backward, setup_context=_dft_setup)
 
 
 # --------------------------------------------------------------------------------------

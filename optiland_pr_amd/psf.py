@@ -11,6 +11,12 @@ formed on the host from the few numbers the reference also reads there (the cent
 126-ray hexapolar trace, the working F/#), uploaded once, and sagged / globalised on the
 device; the PSF and its normalisation stay device tensors. Visualisation (view) is out of
 scope, as everywhere in this package.
+
+FFTPSF (psf/fft.py:20-258) and MMDFTPSF (psf/mmdft.py:19-290): the same Wavefront data
+scattered into the (num_rays, num_rays) pupil grid as a real amplitude and an OPD in waves,
+and the pupil-to-image transform -- the reference's fftshift(fft2(padded pupil)) resp. its
+matrix triple product L g R -- as one fused fp64 DFT, torch.ops.ort.dft_psf (ort_dft_psf,
+csrc/ort_k_dft.hip), which forms the complex pupil and the twiddles on chip.
 """
 
 from __future__ import annotations
@@ -155,3 +161,149 @@ class HuygensPSF(Wavefront):
 
     def _get_working_FNO(self):
         return get_working_FNO(self.optic, self.fields[0], self.wavelengths[0])
+
+
+# --------------------------------------------------------------------------------------
+# FFTPSF / MMDFTPSF (psf/fft.py, psf/mmdft.py)
+# --------------------------------------------------------------------------------------
+def calculate_grid_size(num_rays):
+    """psf/fft.py:20-39: (effective pupil sampling, grid size) of OpticStudio's FFT PSF."""
+    effective_pupil_sampling = np.floor(32 * 2 ** ((np.log2(num_rays) - 5) / 2)).astype(int)
+    return effective_pupil_sampling, num_rays * 2
+
+
+def pupil_grids(intensity, opd_waves, num_rays):
+    """psf/fft.py:140-164 without the exponential: the per-ray intensity and OPD (waves) of a
+    uniform-distribution Wavefront scattered into the linspace(-1, 1, num_rays) meshgrid where
+    R^2 <= 1 (the reference's order, which is the distribution's), zero elsewhere ->
+    (amp, opd), float64 (num_rays, num_rays) tensors on the inputs' device.
+    amp = intensity / mean(intensity[intensity > 0]), all zeros when no ray is valid."""
+    n = int(num_rays)
+    x = np.linspace(-1, 1, n)
+    x, y = np.meshgrid(x, x)
+    inside = torch.as_tensor(np.flatnonzero((x.ravel() ** 2 + y.ravel() ** 2) <= 1),
+                             device=intensity.device)
+    if inside.numel() != intensity.numel() or opd_waves.numel() != intensity.numel():
+        raise ValueError(f"pupil_grids: {intensity.numel()} rays for the {inside.numel()} "
+                         f"points of a uniform pupil grid of {n} x {n}")
+    valid = intensity > 0
+    count = valid.sum()
+    mean = torch.where(valid, intensity, torch.zeros_like(intensity)).sum() / count.clamp(min=1)
+    amplitude = torch.where(count > 0, intensity / mean, torch.zeros_like(intensity))
+    amp = torch.zeros(n * n, dtype=torch.float64, device=intensity.device)
+    opd = torch.zeros_like(amp)
+    amp[inside] = amplitude
+    opd[inside] = opd_waves
+    return amp.reshape(n, n), opd.reshape(n, n)
+
+
+def normalized_dft_psf(amp, opd, image_size, pad_size):
+    """psf/fft.py:194-203, 236-258 / psf/mmdft.py:180-208: dft_psf of one (n, n) pupil or a
+    batch (B, n, n), scaled so that the same aperture with unit amplitude and zero phase peaks
+    at 100: 100 / count_nonzero(amp)^2 per pupil (a device scalar; an empty aperture gives
+    NaN as the reference's 0 / 0 does)."""
+    raw = torch.ops.ort.dft_psf(amp.contiguous(), opd.contiguous(), int(image_size),
+                                float(pad_size))
+    count = (amp != 0).sum(dim=(-2, -1), keepdim=True).to(torch.float64)
+    return raw / (count * count) * 100.0
+
+
+class _PupilPSF(Wavefront):
+    """What FFTPSF and MMDFTPSF share (psf/base.py:51-97): one field, one wavelength, the
+    uniform pupil grid, and the pupil as real (amp, opd) device tensors."""
+
+    def __init__(self, optic, field, wavelength, num_rays, strategy, remove_tilt, **kwargs):
+        super().__init__(optic, fields=[tuple(field)],
+                         wavelengths=[resolve_wavelength(optic, wavelength)],
+                         num_rays=int(num_rays), distribution="uniform", strategy=strategy,
+                         remove_tilt=remove_tilt, **kwargs)
+        data = self.get_data(self.fields[0], self.wavelengths[0])
+        self._amp, self._opd = pupil_grids(data.intensity, data.opd, self.num_rays)
+        self._pupil = None
+
+    def _complex_pupil(self):
+        """psf/fft.py:161-164: amp exp(-2 pi i opd), complex128 -- for the attribute only (the
+        transform never reads it)."""
+        if self._pupil is None:
+            self._pupil = torch.polar(self._amp, -2.0 * np.pi * self._opd)
+        return self._pupil
+
+    def _get_working_FNO(self):
+        return get_working_FNO(self.optic, self.fields[0], self.wavelengths[0])
+
+
+class FFTPSF(_PupilPSF):
+    """psf/fft.py:42-258 on the device. Attributes as the reference's: psf (float64 device
+    tensor [grid_size, grid_size]), pupils (a list of one complex128 [num_rays, num_rays]
+    tensor, built on first access), grid_size, num_rays."""
+
+    def __init__(self, optic, field, wavelength, num_rays=128, grid_size=None,
+                 strategy="chief_ray", remove_tilt=False, **kwargs):
+        if grid_size is None:
+            if num_rays < 32:
+                raise ValueError("num_rays must be at least 32 if grid_size is not specified.")
+            num_rays, grid_size = calculate_grid_size(num_rays)
+        elif grid_size < num_rays:
+            raise ValueError(f"Grid size ({grid_size}) must be greater than or equal to the "
+                             f"number of rays ({num_rays}).")
+        super().__init__(optic, field, wavelength, num_rays, strategy, remove_tilt, **kwargs)
+        self.grid_size = int(grid_size)
+        self.psf = normalized_dft_psf(self._amp, self._opd, self.grid_size,
+                                      float(self.grid_size))
+
+    @property
+    def pupils(self):
+        return [self._complex_pupil()]
+
+    def strehl_ratio(self):
+        """psf/base.py:418-458: the centre pixel / 100."""
+        if self.psf is None:
+            raise RuntimeError("PSF has not been computed.")
+        strehl = self.psf[self.psf.shape[0] // 2, self.psf.shape[1] // 2] / 100
+        return float(strehl.item())
+
+
+class MMDFTPSF(_PupilPSF):
+    """psf/mmdft.py:19-290 on the device. Attributes as the reference's: psf (float64 device
+    tensor [image_size, image_size]), pupil (complex128 [num_rays, num_rays], built on first
+    access), image_size, pixel_pitch (um), num_rays. Where the reference multiplies by its
+    raw `wavelength` argument this uses the resolved wavelength, so "primary" works."""
+
+    def __init__(self, optic, field, wavelength, num_rays=128, image_size=None,
+                 pixel_pitch=None, strategy="chief_ray", remove_tilt=False, **kwargs):
+        grid_size = None
+        if image_size is None and pixel_pitch is None:
+            if num_rays < 32:
+                raise ValueError("num_rays must be at least 32 if image_size and pixel_pitch "
+                                 "are not specified.")
+            num_rays, grid_size = calculate_grid_size(num_rays)
+        super().__init__(optic, field, wavelength, num_rays, strategy, remove_tilt, **kwargs)
+        # :90-117: the three-way resolution of image_size and pixel_pitch
+        span = self.wavelengths[0] * self._get_working_FNO() * (self.num_rays - 1)
+        if pixel_pitch is None:
+            if image_size is None:
+                image_size = grid_size
+            pixel_pitch = span / image_size
+        if image_size is None:
+            image_size = int(span / pixel_pitch)
+        self.image_size = image_size
+        self.pixel_pitch = pixel_pitch
+        # :246-261
+        pad_size = span / self.pixel_pitch
+        if self.image_size > pad_size:
+            max_size = int(pad_size)
+            raise ValueError(f"Supplied image_size of {self.image_size} not less than or equal "
+                             f"to calculated pad size of {max_size}. Consider increasing "
+                             "num_rays.")
+        self.pad_size = float(pad_size)
+        self.psf = normalized_dft_psf(self._amp, self._opd, int(self.image_size), self.pad_size)
+
+    @property
+    def pupil(self):
+        return self._complex_pupil()
+
+    def strehl_ratio(self):
+        """psf/mmdft.py:210-228: max(psf) / 100 (the PSF may not be centred)."""
+        if self.psf is None:
+            raise RuntimeError("PSF has not been computed.")
+        return float((torch.max(self.psf) / 100).item())
