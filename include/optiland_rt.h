@@ -1151,6 +1151,51 @@ int ort_bsdf_scatter(const double* L, const double* M, const double* N, const do
                      const ort_bsdf* bsdf, const ort_scatter* scat, double* out_L,
                      double* out_M, double* out_N, int32_t* status, void* stream);
 
+/* ---- Lens ensembles (tolerancing/monte_carlo.py, sensitivity_analysis.py: thousands of
+ * slightly different lenses with a few hundred rays each; added within v21: a new struct
+ * and entry points only).
+ *
+ * V variants of one lens traced in one launch, RayOperand.rms_spot_size (optimization/
+ * operand/ray.py:300-340: every ray counts, global coordinates) reduced per (variant, pair)
+ * on the device. Under this entry the per-variant tables of `lens` are stacked:
+ *   lens->surfaces           [V][n_surfaces]
+ *   lens->optics             [V][n_lambda][n_surfaces]
+ *   lens->n_tab, alpha_tab   [V][n_lambda][n_mat]
+ *   lens->cs_ops             [V][cs_stride]; a variant's cs_loc_off / cs_glob_off are relative
+ *                            to its own block (the op counts may differ per variant)
+ * coef, zern, materials and wavelengths are shared, and frame_flags / form_flags must hold
+ * for EVERY variant. The n_pupil pupil points are shared; seg holds [V][P] segments (each
+ * variant's own ray-generation scalars). A workgroup of 256 threads traces one chunk of one
+ * (variant, pair) -- the tail lanes of a pair's last chunk idle -- so the surface record and
+ * the optics row are wave-uniform scalar loads exactly as in ort_trace_pupil, whose rays this
+ * entry reproduces bit for bit (ray p of (variant v, pair q) at index (v P + q) n_pupil + p
+ * of the eight arrays of rays_out; rays_out NULL: no ray is stored).
+ *
+ * stats [V][P][5]: count, mean x, mean y, rms, NaN (ort_rms_spot's row without the geometric
+ * radius). Every workgroup writes the row {n, sum x, sum y, M2 about its own centroid} of
+ * its chunk into the workspace ([V P chunks][4] doubles from its start, chunks =
+ * ceil(n_pupil / 256)); a second launch combines each (variant, pair)'s rows in index order
+ * (ort_rms_finish's workgroup). Fixed-order sums, no atomics but the status word's OR:
+ * bit-identical run to run. A NaN ray makes its own pair's mean and rms NaN and touches
+ * nothing else.
+ *
+ * ORT_ERR_ARG ("unsupported"): a geometry_mask beyond plane | standard, an interaction_mask
+ * beyond ORT_IA_REFRACT_REFLECT, n_pupil < 1, V P chunks >= 2^31, null pointers, a short
+ * workspace. status (nullable, device int32) is initialised by this call. */
+typedef struct ort_ensemble {
+  int32_t n_variants;            /* V >= 1 */
+  int32_t pairs;                 /* P: (field, wavelength) segments per variant */
+  int32_t cs_stride;             /* ort_cs_op records per variant in lens->cs_ops */
+  int32_t reserved;
+  const double* final_thickness; /* device, nullable [V]; NULL: lens->final_thickness */
+} ort_ensemble; /* 24 bytes */
+/* Bytes of device workspace ort_trace_ensemble needs (< 0: ORT_ERR_ARG). */
+int64_t ort_ensemble_workspace_size(const ort_ensemble* e, int64_t n_pupil);
+int ort_trace_ensemble(const ort_lens* lens, const ort_ensemble* e, const double* px,
+                       const double* py, int64_t n_pupil, const ort_segment* seg,
+                       const ort_apodization* apod, ort_rays* rays_out, double* stats,
+                       void* workspace, int64_t workspace_size, int32_t* status, void* stream);
+
 /* Error codes */
 enum ort_error {
   ORT_OK = 0,

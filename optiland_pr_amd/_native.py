@@ -153,6 +153,16 @@ class ort_scatter(C.Structure):  # added within v21 (ort_trace_*_scatter, ort_bs
     ]
 
 
+class ort_ensemble(C.Structure):  # added within v21 (ort_trace_ensemble)
+    _fields_ = [
+        ("n_variants", C.c_int32),
+        ("pairs", C.c_int32),
+        ("cs_stride", C.c_int32),
+        ("reserved", C.c_int32),
+        ("final_thickness", C.c_void_p),
+    ]
+
+
 class ort_spot_layout(C.Structure):
     _fields_ = [
         ("n_pupil", C.c_int64),
@@ -176,6 +186,7 @@ PTR, I32, I64, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 LENS, RAYS, BATCH, OPTIONS = (C.POINTER(s) for s in (ort_lens, ort_rays, ort_batch, ort_options))
 VJP, POL, SPOT = (C.POINTER(s) for s in (ort_vjp_params, ort_polarization, ort_spot_layout))
 SCAT = C.POINTER(ort_scatter)
+ENSEMBLE = C.POINTER(ort_ensemble)
 
 DEVICE_PROTOTYPES = {
     "ort_abi_version": (C.c_int, []),
@@ -231,6 +242,9 @@ DEVICE_PROTOTYPES = {
                                                SCAT, PTR]),
     "ort_bsdf_scatter": (C.c_int, [PTR, PTR, PTR, PTR, PTR, PTR, I64, I32, PTR, SCAT, PTR, PTR,
                                    PTR, PTR, PTR]),
+    "ort_ensemble_workspace_size": (I64, [ENSEMBLE, I64]),
+    "ort_trace_ensemble": (C.c_int, [LENS, ENSEMBLE, PTR, PTR, I64, PTR, PTR, RAYS, PTR, PTR, I64,
+                                     PTR, PTR]),
 }
 
 HOST_PROTOTYPES = {

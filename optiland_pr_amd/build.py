@@ -30,7 +30,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "ort_k_adj.hip", "ort_k_adj2.hip", "ort_k_adj4.hip", "ort_k_adj2r.hip", "ort_k_adj4r.hip", "ort_k_pupil.hip", "ort_k_trace_ia.hip",
     "ort_k_spot.hip", "ort_k_wavefront.hip", "ort_k_huygens.hip", "ort_k_irradiance.hip",
     "ort_k_dft.hip",
-    "ort_k_trace_pol.hip", "ort_k_trace_scat.hip")]
+    "ort_k_trace_pol.hip", "ort_k_trace_scat.hip", "ort_k_ensemble.hip")]
 HEADERS = [os.path.join(CSRC, "ort_core.h"), os.path.join(CSRC, "ort_args.h"), os.path.join(CSRC, "ort_kernels.h"), os.path.join(CSRC, "ort_fastpath.h"),
            os.path.join(CSRC, "ort_adjoint.h"), os.path.join(CSRC, "ort_pupil.h"),
            os.path.join(CSRC, "ort_sincos_table.h"), os.path.join(CSRC, "ort_material.h"), os.path.join(CSRC, "ort_interact.h"), os.path.join(CSRC, "ort_reduce.h"),

@@ -1530,3 +1530,58 @@ def _scatter_backward(ctx, *grads):
 trace_pupil_scatter.register_autograd(_scatter_backward)
 trace_sequential_scatter.register_autograd(_scatter_backward)
 bsdf_scatter.register_autograd(_scatter_backward)
+
+
+# --------------------------------------------------------------------------------------
+# ort::trace_ensemble -- V variants of one lens in one launch (ort_trace_ensemble,
+# tolerancing.py): the stacked tables in, the per-(variant, pair) rms rows and, on request,
+# the rays out. Device only: the host build traces one lens per call.
+# --------------------------------------------------------------------------------------
+ENSEMBLE_META = ("n_surfaces", "n_lambda", "n_mat", "final_mat", "geometry_mask",
+                 "interaction_mask", "frame_flags", "form_flags", "n_variants", "pairs",
+                 "cs_stride")
+
+
+@torch.library.custom_op("ort::trace_ensemble", mutates_args=(), device_types="cuda")
+def trace_ensemble(lens: list[torch.Tensor], lens_meta: list[int], final_thickness: torch.Tensor,
+                   seg: torch.Tensor, apod: torch.Tensor | None, px: torch.Tensor,
+                   py: torch.Tensor, want_rays: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """lens: the nine tables of tolerancing.EnsembleTable.tensors (surfaces [V][S], cs_ops
+    [V][cs_stride], coef, zern, n_tab and alpha_tab [V][n_lambda][n_mat], optics
+    [V][n_lambda][S], materials, wavelengths); lens_meta: ENSEMBLE_META; final_thickness [V];
+    seg: [V][P] SEGMENT records as bytes; px, py: the shared pupil points. Returns stats
+    [V, P, 4] (count, mean x, mean y, rms: the C row without its constant NaN column) and the
+    rays [8, V * P * n_pupil] (x y z L M N i opd; [8, 0] without want_rays). Forward only."""
+    from . import tolerancing
+    from .raytrace import _raise_status_value
+
+    if len(lens_meta) != len(ENSEMBLE_META) or len(lens) != 9:
+        raise ValueError("trace_ensemble: lens holds nine tables, lens_meta ENSEMBLE_META")
+    V, P = lens_meta[8], lens_meta[9]
+    if seg.numel() != V * P * _abi.SEGMENT.itemsize or final_thickness.numel() != V:
+        raise ValueError("trace_ensemble: seg holds [V][P] segments, final_thickness [V]")
+    stats, rays, status = tolerancing.trace_ensemble(
+        [t.detach().contiguous() for t in lens], [int(v) for v in lens_meta],
+        final_thickness.detach().to(torch.float64).contiguous(), seg.contiguous(),
+        apod, px.detach().contiguous(), py.detach().contiguous(), bool(want_rays))
+    if apod is not None:  # only an apodization record can raise a status bit here
+        _raise_status_value(int(status.item()))
+    if rays is None:
+        rays = px.new_empty((8, 0), dtype=torch.float64)
+    return stats[..., :4].contiguous(), rays
+
+
+@trace_ensemble.register_fake
+def _(lens, lens_meta, final_thickness, seg, apod, px, py, want_rays):
+    V, P = lens_meta[8], lens_meta[9]
+    n = V * P * px.numel() if want_rays else 0
+    return (px.new_empty((V, P, 4), dtype=torch.float64),
+            px.new_empty((8, n), dtype=torch.float64))
+
+
+def _ensemble_backward(ctx, *grads):
+    raise RuntimeError("ort::trace_ensemble is forward only: autograd through the lens-ensemble "
+                       "trace is not implemented")
+
+
+trace_ensemble.register_autograd(_ensemble_backward)
