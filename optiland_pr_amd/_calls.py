@@ -1,13 +1,21 @@
 """The Python call layer of the two C ABIs: the argument structs of include/optiland_rt.h
-(and of include/optiland_host.h, which takes the same ones) built from tensors, once, for
-raytrace.py, autodiff.py, ops.py, host.py, polarization.py and distributed.py -- the Python
-counterpart of csrc/ort_args.h, which reads these structs for both libraries. Flat
-functions over _native's ctypes structs; no torch ops and no launches here.
+(and of include/optiland_host.h, which takes the same ones) built from tensors, and the one
+place that knows how a forward-trace entry point is called -- the Python counterpart of
+csrc/ort_args.h, which reads these structs for both libraries.
+
+FORWARD names the 12 forward entries (device / host, pupil / sequential, plain / polarized /
+scatter) with their two signature differences, call_forward builds their argument list and
+makes the call, and raise_status turns the status word any of them leaves into its
+exception. Only raytrace.py (device) and host.py (host) call a forward entry; polarization.py,
+scatter.py, ops.py and tolerancing.py build their extra struct and hand it to those two.
+Flat functions over _native's ctypes structs: no torch ops and no GPU-runtime calls here,
+only the library call a caller hands in.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -25,6 +33,23 @@ def addr(t):
     if t is None:
         return None
     return t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data
+
+
+def bytes_tensor(arr):
+    """A numpy array's bytes (a structured table: its records) as a uint8 CPU tensor of its
+    own memory."""
+    return torch.from_numpy(np.frombuffer(np.ascontiguousarray(arr).tobytes(),
+                                          dtype=np.uint8).copy())
+
+
+def segments_of(lens, segs):
+    """The SEGMENT records of a generating launch on the lens's device (DeviceLens or
+    HostLens): a tensor goes as it is, a host array through lens.resident (no copy while
+    its bytes are unchanged). The caller keeps the result alive until its launch is
+    enqueued."""
+    if torch.is_tensor(segs):
+        return segs
+    return lens.resident("segments", np.asarray(segs, dtype=_abi.SEGMENT))
 
 
 def rays_struct(ts):
@@ -55,6 +80,117 @@ def resident_batch(n, group_len=None, seg=None, seg_len=None):
     (seg / seg_len: per-segment wavelength rows, as pupil_batch). Per-ray wavelengths go
     into its `w` field (per_ray_wavelengths)."""
     return _batch(n, seg_len or max(n, 1), group_len or max(n, 1), seg, False, None)
+
+
+class ForwardEntry(NamedTuple):
+    """One forward-trace entry point: its symbol and what its signature differs in."""
+    name: str
+    kind: str       # "pupil": (px, py) generate the rays; "sequential": resident rays_in
+    host: bool      # update counts where the device takes Newton statistics; no stream
+    has_rec: bool   # False for ort_host_trace_pupil alone: a `rec` given there is dropped
+
+
+# (library, kind, extra) -> ForwardEntry; extra: None, "polarized" (an ort_polarization
+# follows the status) or "scatter" (an ort_scatter does)
+FORWARD = {
+    (library, kind, extra): ForwardEntry(name, kind, library == "host",
+                                         name != "ort_host_trace_pupil")
+    for library, kind, extra, name in (
+        ("device", "pupil", None, "ort_trace_pupil"),
+        ("device", "pupil", "polarized", "ort_trace_pupil_polarized"),
+        ("device", "pupil", "scatter", "ort_trace_pupil_scatter"),
+        ("device", "sequential", None, "ort_trace_sequential"),
+        ("device", "sequential", "polarized", "ort_trace_sequential_polarized"),
+        ("device", "sequential", "scatter", "ort_trace_sequential_scatter"),
+        ("host", "pupil", None, "ort_host_trace_pupil"),
+        ("host", "pupil", "polarized", "ort_host_trace_pupil_polarized"),
+        ("host", "pupil", "scatter", "ort_host_trace_pupil_scatter"),
+        ("host", "sequential", None, "ort_host_trace_sequential"),
+        ("host", "sequential", "polarized", "ort_host_trace_sequential_polarized"),
+        ("host", "sequential", "scatter", "ort_host_trace_sequential_scatter"),
+    )}
+GENERATE = {"device": "ort_generate_rays", "host": "ort_host_generate_rays"}
+
+
+def forward_entry(library, kind, pol=None, scat=None):
+    """(the FORWARD entry, its extra struct) of a trace with an optional ort_polarization
+    or ort_scatter (one dict hit; no entry takes both)."""
+    if pol is not None:
+        if scat is not None:
+            raise ValueError("BSDF surfaces together with coatings or a polarization state "
+                             "are not supported")
+        return FORWARD[library, kind, "polarized"], pol
+    if scat is not None:
+        return FORWARD[library, kind, "scatter"], scat
+    return FORWARD[library, kind, None], None
+
+
+def call_forward(lib, entry, lens_c, src, out_c, batch, opt, rec, counts, status, extra=None,
+                 stream=None):
+    """Call a FORWARD entry of `lib` and check its return code. src: (px, py) for a pupil
+    entry, the ort_rays of the resident rays for a sequential one; counts: the Newton
+    statistics (device) or update counts (host); extra: the entry's ort_polarization /
+    ort_scatter; stream: the device entries' last argument."""
+    name, kind, host, has_rec = entry
+    args = [C.byref(lens_c)]
+    args += (addr(src[0]), addr(src[1])) if kind == "pupil" else (C.byref(src),)
+    args += (C.byref(out_c), C.byref(batch), C.byref(opt))
+    if has_rec:
+        args.append(addr(rec))
+    args += (addr(counts), addr(status))
+    if extra is not None:
+        args.append(C.byref(extra))
+    if not host:
+        args.append(stream)
+    _native.check(getattr(lib, name)(*args), name)
+
+
+def call_generate(lib, library, px, py, out_c, batch, stream=None):
+    """ort_generate_rays / ort_host_generate_rays (GENERATE[library]) of `lib`."""
+    name = GENERATE[library]
+    args = [addr(px), addr(py), C.byref(out_c), C.byref(batch)]
+    if library == "device":
+        args.append(stream)
+    _native.check(getattr(lib, name)(*args), name)
+
+
+class ZernikeRangeError(ValueError):
+    pass
+
+
+class ChebyshevRangeError(ValueError):
+    pass
+
+
+_CHEBYSHEV_MSG = ("Chebyshev input coordinates must be normalized to [-1, 1]. Consider "
+                  "updating the normalization factors.")  # chebyshev.py:203-215
+_ZERNIKE_MSG = ("Zernike coordinates must be normalized to [-1, 1]. Consider updating the "
+                "normalization radius to 1.1x the surface aperture.")
+
+
+def raise_status(v, table=None, max_attempts=None):
+    """The exception of a status word (ORT_STATUS_* bits) a trace left, for both libraries
+    and the deferred device checks; nothing for 0. table / max_attempts: the traced
+    LensTable and its scatter_max_attempts -- with BSDF surfaces a used-up rejection loop
+    is reported by surface and sigma."""
+    if not v:
+        return
+    if v & _abi.STATUS_BAD_APODIZATION:
+        raise ValueError("the apodization record holds a kind the trace core does not know")
+    if v & _abi.STATUS_BAD_GEOMETRY:
+        raise ValueError("the lens table holds a geometry id the trace core does not know "
+                         "(library / host ABI mismatch?)")
+    if v & _abi.STATUS_ZERNIKE_RANGE:
+        raise ZernikeRangeError(_ZERNIKE_MSG)
+    if v & _abi.STATUS_CHEBYSHEV_RANGE:
+        raise ChebyshevRangeError(_CHEBYSHEV_MSG)
+    if v & _abi.STATUS_SCATTER_ATTEMPTS:
+        from . import scatter
+
+        if table is not None and table.has_bsdf:
+            raise scatter.attempts_error(scatter.describe(table),
+                                         max_attempts or scatter.DEFAULT_MAX_ATTEMPTS)
+        raise scatter.ScatterAttemptsError("BSDF scattering used up its attempts")
 
 
 def decreasing_tables(table):

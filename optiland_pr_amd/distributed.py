@@ -250,10 +250,8 @@ class PipelinedImageTrace:
         for lo, hi in zip(bounds[:-1], bounds[1:], strict=True):
             if hi == lo:
                 continue
-            sub = RealRays.__new__(RealRays)
-            for a in ("x", "y", "z", "L", "M", "N", "i", "opd"):
-                setattr(sub, a, getattr(self.out, a)[lo * nl:hi * nl])
-            sub.w = self.out.w
+            sub = RealRays.of([getattr(self.out, a)[lo * nl:hi * nl]
+                               for a in ("x", "y", "z", "L", "M", "N", "i", "opd")], self.out.w)
             self.chunks.append((int(lo), int(hi), upload_segments(segs[lo:hi], dlens.device),
                                 px[lo * nl:hi * nl], py[lo * nl:hi * nl], sub))
 
@@ -410,10 +408,7 @@ def spot_statistics(x, y, i, n_fields, n_wl, ref_wl_index, group=None, z=None):
 
     n_pairs = n_fields * n_wl
     n_loc = x.numel() // max(1, n_pairs)
-    r = RealRays.__new__(RealRays)
-    r.x, r.y, r.i = x, y, i
-    r.z = z if z is not None else x
-    r.L = r.M = r.N = r.opd = x
+    r = RealRays.of([x, y, z if z is not None else x, x, x, x, i, x])
     st = ShardedSpotStatistics(n_fields, n_wl, n_loc, ref_wl_index, device=x.device,
                                group=group)
     return st.run(r)[1]

@@ -9,6 +9,12 @@ uploads); the calls below hand host pointers to the C ABI of the host library, w
 the GPU kernels' per-ray source compiled with g++ (csrc/ort_host.cpp). This is not a
 fallback of the device path: device tensors never come here, and host tensors never reach
 the HIP library.
+
+trace_pupil and trace_sequential are the only callers of the host library's six forward
+entries (plain, polarized, scatter), through _calls.FORWARD / call_forward and the one
+status path _calls.raise_status; raytrace.py is their counterpart for the device library.
+The scatter struct comes from the lens, a polarization struct from the caller
+(polarization.py).
 """
 
 from __future__ import annotations
@@ -62,6 +68,8 @@ class HostLens:
         self._tensors = [torch.from_numpy(a.view(np.uint8) if a.dtype.fields else a)
                          for a in (surfaces, cs_ops, coef, zern, n_tab.reshape(-1),
                                    alpha_tab.reshape(-1), optics.reshape(-1), mats, lambdas)]
+        # the pupil apodization record (ort_batch.apod of generating calls), as DeviceLens.apod
+        self.apod = None if table.apod is None else _calls.bytes_tensor(table.apod)
         self.newton = table.newton_surfaces
         self.last_schedule = None
         self.last_schedule_dev = None
@@ -81,63 +89,56 @@ class HostLens:
         hit = self._resident.get(slot)
         if hit is not None and hit[0] == raw and hit[1] == a.dtype:
             return hit[2]
-        t = torch.from_numpy(a.copy())
+        # (a structured table: its records' bytes)
+        t = _calls.bytes_tensor(a) if a.dtype.fields is not None else torch.from_numpy(a.copy())
         self._resident[slot] = (raw, a.dtype, t)
         return t
 
 
-def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec, ray_offset=0):
-    """ort_host_trace_sequential of resident CPU rays (8 contiguous float64 tensors):
-    returns the 8 output tensors and the Newton update counts [S] (int32 tensor) the
-    reference's stop rule made."""
-    from .raytrace import _raise_status_value
-
-    lib = _native.load_host()
-    n = rays_in[0].numel()
-    outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
-    batch = _calls.resident_batch(n)
-    w_keep = None
-    if per_ray_w:
-        w_keep = _calls.per_ray_wavelengths(hl.table, w, n, hl.device, validate=True)
-        batch.w = addr(w_keep)
-    S = hl.table.n_surfaces
-    updates = torch.zeros(S, dtype=torch.int32)
-    status = np.zeros(1, dtype=np.int32)
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
-    rin_c, out_c = rays_struct(rays_in), rays_struct(outs)
-    if hl.table.has_bsdf:  # ort_host_trace_sequential_scatter (ray r draws as r + ray_offset)
-        if per_ray_w:
-            raise ValueError("BSDF surfaces trace one wavelength per call")
-        scat = _scatter_struct(hl, ray_offset)
-        rc = lib.ort_host_trace_sequential_scatter(
-            C.byref(hl.c), C.byref(rin_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-            addr(rec), addr(updates), addr(status), C.byref(scat[0]))
-        _native.check(rc, "ort_host_trace_sequential_scatter")
-        _raise_scatter_status(hl, scat, int(status[0]))
-        return outs, updates
-    rc = lib.ort_host_trace_sequential(C.byref(hl.c), C.byref(rin_c), C.byref(out_c),
-                                       C.byref(batch), C.byref(opt), addr(rec),
-                                       addr(updates), addr(status))
-    _native.check(rc, "ort_host_trace_sequential")
-    _raise_status_value(int(status[0]))
-    return outs, updates
-
-
-def _scatter_struct(hl, ray_offset):
+def _scatter_of(hl, ray_offset):
+    """(ort_scatter, its records) of a lens with BSDF surfaces, else None."""
+    if not hl.table.has_bsdf:
+        return None
     from . import scatter
 
     return scatter.scatter_struct(hl, ray_offset)
 
 
-def _raise_scatter_status(hl, scat, status):
-    """_raise_status_value, a used-up rejection loop reported by surface and sigma."""
-    from . import scatter
-    from .raytrace import _raise_status_value
+def _forward(hl, kind, src, outs, batch, start_surface, rec, updates, pol, scat):
+    """One forward entry of the host library (_calls.FORWARD) and its status check. scat:
+    _scatter_of's pair, kept alive through the call."""
+    entry, extra = _calls.forward_entry("host", kind, pol, scat and scat[0])
+    status = np.zeros(1, dtype=np.int32)
+    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
+    _calls.call_forward(_native.load_host(), entry, hl.c, src, rays_struct(outs), batch, opt,
+                        rec, updates, status, extra)
+    _calls.raise_status(int(status[0]), hl.table, scat and scat[0].max_attempts)
 
-    try:
-        _raise_status_value(status)
-    except scatter.ScatterAttemptsError:
-        raise scatter.attempts_error(scatter.describe(hl.table), scat[0].max_attempts) from None
+
+def trace_sequential(hl: HostLens, rays_in, w, per_ray_w, start_surface, rec, ray_offset=0,
+                     pol=None, outs=None):
+    """ort_host_trace_sequential of resident CPU rays (8 contiguous float64 tensors):
+    returns the 8 output tensors (outs: preallocated ones) and the Newton update counts [S]
+    (int32 tensor) the reference's stop rule made. A lens with BSDF surfaces takes
+    ort_host_trace_sequential_scatter (ray r draws as r + ray_offset); pol, the
+    ort_polarization of a lens lowered with polarized=True (its caller keeps the coatings
+    and planes alive), ort_host_trace_sequential_polarized."""
+    n = rays_in[0].numel()
+    if outs is None:
+        outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
+    batch = _calls.resident_batch(n)
+    w_keep = None
+    if per_ray_w:
+        w_keep = _calls.per_ray_wavelengths(hl.table, w, n, hl.device, validate=True)
+        batch.w = addr(w_keep)
+    updates = torch.zeros(hl.table.n_surfaces, dtype=torch.int32)
+    scat = _scatter_of(hl, ray_offset)
+    if scat is not None and per_ray_w:
+        raise ValueError("BSDF surfaces trace one wavelength per call")
+    _forward(hl, "sequential", rays_struct(rays_in), outs, batch, start_surface, rec, updates,
+             pol, scat)
+    del w_keep  # (read by the call above)
+    return outs, updates
 
 
 def trace_sequential_vjp(hl: HostLens, rays_in, w, per_ray_w, start_surface, sched, tabs,
@@ -164,35 +165,23 @@ def trace_sequential_vjp(hl: HostLens, rays_in, w, per_ray_w, start_surface, sch
 
 
 def trace_pupil(hl: HostLens, seg, px, py, n, seg_len, pupil_per_ray, apod=None, ray_offset=0,
-                rec=None):
+                rec=None, pol=None, outs=None):
     """ort_host_trace_pupil: rays generated from the pupil samples by the segments (SEGMENT
-    records as a uint8 CPU tensor) and traced as one reference trace call (one Newton
-    group); returns the 8 output tensors and the update counts [S] (int32)."""
-    from .raytrace import _raise_status_value
-
-    lib = _native.load_host()
-    outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
+    records as a uint8 CPU tensor, or a host array) and traced as one reference trace call
+    (one Newton group); returns the 8 output tensors (outs: preallocated ones) and the update
+    counts [S] (int32). BSDF surfaces / pol: the _scatter / _polarized entry, as
+    trace_sequential; rec ([n_rec][8][n] or None) is theirs -- the plain entry has none."""
+    if outs is None:
+        outs = [torch.empty(n, dtype=torch.float64) for _ in range(8)]
     # one Newton group: the whole call, as RealRayTracer.trace traces every field of a
     # wavelength in one SurfaceGroup.trace (real_ray_tracer.py:37-97)
+    seg = _calls.segments_of(hl, seg)  # (kept alive through the call, as apod by the caller)
     batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
     S = hl.table.n_surfaces
     n_groups = 1 if n else 0
     updates = torch.zeros(max(1, n_groups) * S, dtype=torch.int32)
-    status = np.zeros(1, dtype=np.int32)
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
-    out_c = rays_struct(outs)
-    if hl.table.has_bsdf:  # ort_host_trace_pupil_scatter (rec: [n_rec][8][n] or None)
-        scat = _scatter_struct(hl, ray_offset)
-        rc = lib.ort_host_trace_pupil_scatter(
-            C.byref(hl.c), addr(px), addr(py), C.byref(out_c), C.byref(batch), C.byref(opt),
-            addr(rec), addr(updates), addr(status), C.byref(scat[0]))
-        _native.check(rc, "ort_host_trace_pupil_scatter")
-        _raise_scatter_status(hl, scat, int(status[0]))
-        return outs, updates[:n_groups * S]
-    rc = lib.ort_host_trace_pupil(C.byref(hl.c), addr(px), addr(py), C.byref(out_c),
-                                  C.byref(batch), C.byref(opt), addr(updates), addr(status))
-    _native.check(rc, "ort_host_trace_pupil")
-    _raise_status_value(int(status[0]))
+    _forward(hl, "pupil", (px, py), outs, batch, 0, rec, updates, pol,
+             _scatter_of(hl, ray_offset))
     return outs, updates[:n_groups * S]
 
 

@@ -384,13 +384,10 @@ def trace_sequential(lens: list[torch.Tensor], lens_meta: list[int], final_thick
         raise ValueError("rays: x, y, z, L, M, N, i, opd")
     n = rays[0].numel()
     dev = dl.device
-    rin = RealRays.__new__(RealRays)
-    for a, t in zip(_abi.RAY_FIELDS, rays, strict=True):
-        setattr(rin, a, t.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous())
-    rin.w = w.detach() if w is not None else torch.zeros(1, dtype=torch.float64, device=dev)
-    rout = RealRays.__new__(RealRays)
-    for a in _abi.RAY_FIELDS:
-        setattr(rout, a, torch.empty(n, dtype=torch.float64, device=dev))
+    rin = RealRays.of(
+        [t.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous() for t in rays],
+        w.detach() if w is not None else torch.zeros(1, dtype=torch.float64, device=dev))
+    rout = RealRays.of([torch.empty(n, dtype=torch.float64, device=dev) for _ in range(8)])
     n_rec = dl.table.n_rec
     rec = torch.empty(n_rec * 8 * n, dtype=torch.float64, device=dev)
     trace_rays(dl, rin, rout, rec=rec if n_rec else None, start_surface=int(start_surface),
@@ -609,12 +606,8 @@ def plan_args(plan):
     pupil_per_ray, newton mode index, want_tape, want_rms] and the plan's handle (its Newton
     schedule cache keys; a cache key only)."""
     dl = plan.dlens
-    seg = plan.seg_dev
-    if not torch.is_tensor(seg):
-        seg = dl.resident("segments", np.asarray(seg, dtype=_abi.SEGMENT))
-    apod = getattr(dl, "apod", None)
-    if apod is None and getattr(dl.table, "apod", None) is not None and dl.device.type == "cpu":
-        apod = dl.resident("apod", dl.table.apod)
+    seg = _calls.segments_of(dl, plan.seg_dev)
+    apod = dl.apod
     meta = [plan.n, plan.seg_len, int(plan.pupil_per_ray),
             NEWTON_MODES.index(plan.newton_mode), int(bool(plan.want_tape)),
             int(bool(plan.want_rms))]
@@ -654,9 +647,7 @@ def trace_pupil(lens: list[torch.Tensor], lens_meta: list[int], final_thickness:
     want_rms = _want_rms(plan_meta)
     if want_rms and not want_tape:
         raise ValueError("ort::trace_pupil: want_rms needs the taped forward (want_tape)")
-    out = RealRays.__new__(RealRays)
-    for a in _abi.RAY_FIELDS:
-        setattr(out, a, torch.empty(n, dtype=torch.float64, device=dl.device))
+    out = RealRays.of([torch.empty(n, dtype=torch.float64, device=dl.device) for _ in range(8)])
     tape = torch.empty(tape_doubles(dl, n) if want_tape else 0, dtype=torch.float64,
                        device=dl.device)
     rms = torch.empty(() if want_rms else 0, dtype=torch.float64, device=dl.device)
@@ -1297,15 +1288,11 @@ def polarized_args(lens, segs, px, py, n, seg_len, mode, state, pupil_per_ray=Fa
     from . import polarization as pz
 
     L, meta, ft, key = lens_args(lens)
-    dev = lens.device
-    coat = pz._coatings_of(lens)
-    seg = segs if torch.is_tensor(segs) else pz._bytes_tensor(
-        np.asarray(segs, dtype=_abi.SEGMENT)).to(dev)
-    apod = pz._apod_of(lens)
     ex = ey = 0j
     if mode == _abi.POL_POLARIZED:
         ex, ey = state.field()
-    return (L, meta, ft, key, coat, seg, apod, px, py,
+    return (L, meta, ft, key, pz._coatings_of(lens), _calls.segments_of(lens, segs), lens.apod,
+            px, py,
             [ex.real, ex.imag, ey.real, ey.imag],
             [int(n), int(seg_len), int(bool(pupil_per_ray)), int(mode), int(bool(want_p))])
 
@@ -1373,17 +1360,13 @@ def scatter_args(lens, segs, px, py, n, seg_len, pupil_per_ray=False, ray_offset
     table with BSDF surfaces: the lens tensors, its BSDF records and the SEGMENT /
     APODIZATION records as uint8 tensors on the lens's device, the pupil, the seed
     (lens.scatter) and plan_meta = [n, seg_len, pupil_per_ray, ray_offset, max_attempts]."""
-    from . import polarization as pz
     from . import scatter as sc
 
     L, meta, ft, key = lens_args(lens, scatter=True)
-    dev = lens.device
-    bsdf = lens.resident("bsdf", np.ascontiguousarray(lens.table.bsdf).view(np.uint8))
-    seg = segs if torch.is_tensor(segs) else pz._bytes_tensor(
-        np.asarray(segs, dtype=_abi.SEGMENT)).to(dev)
-    seed, cap = getattr(lens, "scatter", (0, sc.DEFAULT_MAX_ATTEMPTS))
-    return (L, meta, ft, key, bsdf, seg, pz._apod_of(lens), px, py, _seed64(seed),
-            [int(n), int(seg_len), int(bool(pupil_per_ray)), int(ray_offset), int(cap)])
+    sct, bsdf = sc.scatter_struct(lens)  # (the lens's seed and cap; its resident records)
+    return (L, meta, ft, key, bsdf, _calls.segments_of(lens, segs), lens.apod, px, py,
+            _seed64(sct.seed),
+            [int(n), int(seg_len), int(bool(pupil_per_ray)), int(ray_offset), int(sct.max_attempts)])
 
 
 def sequential_scatter_args(lens, rays_in, start_surface=0, ray_offset=0):
@@ -1392,13 +1375,12 @@ def sequential_scatter_args(lens, rays_in, start_surface=0, ray_offset=0):
     from . import scatter as sc
 
     L, meta, ft, key = lens_args(lens, scatter=True)
-    bsdf = lens.resident("bsdf", np.ascontiguousarray(lens.table.bsdf).view(np.uint8))
-    seed, cap = getattr(lens, "scatter", (0, sc.DEFAULT_MAX_ATTEMPTS))
-    return (L, meta, ft, key, bsdf, rays_in, _seed64(seed),
-            [int(start_surface), int(ray_offset), int(cap)])
+    sct, bsdf = sc.scatter_struct(lens)
+    return (L, meta, ft, key, bsdf, rays_in, _seed64(sct.seed),
+            [int(start_surface), int(ray_offset), int(sct.max_attempts)])
 
 
-def _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap, apod=None):
+def _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap):
     """The resolved lens carrying the op's BSDF records, seed and attempt cap (a lens
     rebuilt from its tensors has none of its own)."""
     dl = _resolve(lens, lens_meta, final_thickness, lens_key)
@@ -1406,8 +1388,6 @@ def _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap, a
     if dl.table.bsdf is None or dl.table.bsdf.tobytes() != rec.tobytes():
         dl.table.bsdf = rec
     dl.scatter = (int(seed) & 0xFFFFFFFFFFFFFFFF, int(cap))
-    if apod is not None and dl.device.type != "cpu" and getattr(dl, "apod", None) is None:
-        dl.apod = apod
     return dl
 
 
@@ -1420,22 +1400,13 @@ def trace_pupil_scatter(lens: list[torch.Tensor], lens_meta: list[int], final_th
     (ort_trace_pupil_scatter): the rays [8, n] (x y z L M N i opd). Ray r draws as ray
     r + ray_offset of the stream keyed by `seed`. Forward only: a backward raises."""
     n, seg_len, ppr, ray_offset, cap = plan_meta[:5]
-    dl = _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap, apod)
-    pxc, pyc = px.detach().contiguous(), py.detach().contiguous()
-    if dl.device.type == "cpu":
-        from . import host
-
-        outs, _ = host.trace_pupil(dl, seg, pxc, pyc, n, seg_len, bool(ppr), apod=apod,
-                                   ray_offset=ray_offset)
-        return torch.stack(outs)
     from . import raytrace
 
+    dl = _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap)
     rays = torch.empty((8, n), dtype=torch.float64, device=dl.device)
-    out = raytrace.RealRays.__new__(raytrace.RealRays)
-    for a, t in zip(_abi.RAY_FIELDS, rays.unbind(0), strict=True):
-        setattr(out, a, t)
-    raytrace.trace_pupil(dl, seg, pxc, pyc, out, n, seg_len, max(n, 1),
-                         pupil_per_ray=bool(ppr), ray_offset=ray_offset)
+    raytrace.trace_pupil_on(dl, seg, px.detach().contiguous(), py.detach().contiguous(),
+                            list(rays.unbind(0)), n, seg_len, bool(ppr),
+                            ray_offset=ray_offset, apod=apod)
     return rays
 
 
@@ -1461,21 +1432,12 @@ def trace_sequential_scatter(lens: list[torch.Tensor], lens_meta: list[int],
     (ort_trace_sequential_scatter): the traced rays [8, n]. Forward only."""
     start_surface, ray_offset, cap = plan_meta[:3]
     dl = _scatter_lens(lens, lens_meta, final_thickness, lens_key, bsdf, seed, cap)
-    rin = rays_in.detach().to(torch.float64).contiguous()
-    if dl.device.type == "cpu":
-        from . import host
-
-        outs, _ = host.trace_sequential(dl, list(rin.unbind(0)), None, False, start_surface,
-                                        None, ray_offset=ray_offset)
-        return torch.stack(outs)
     from . import raytrace
 
+    rin = rays_in.detach().to(torch.float64).contiguous()
     rout = torch.empty_like(rin)
-    src, dst = (raytrace.RealRays.__new__(raytrace.RealRays) for _ in range(2))
-    for a, s, d in zip(_abi.RAY_FIELDS, rin.unbind(0), rout.unbind(0), strict=True):
-        setattr(src, a, s)
-        setattr(dst, a, d)
-    raytrace.trace_rays(dl, src, dst, start_surface=start_surface, ray_offset=ray_offset)
+    raytrace.trace_rays_on(dl, list(rin.unbind(0)), list(rout.unbind(0)), start_surface,
+                           ray_offset=ray_offset)
     return rout
 
 
@@ -1553,7 +1515,6 @@ def trace_ensemble(lens: list[torch.Tensor], lens_meta: list[int], final_thickne
     [V, P, 4] (count, mean x, mean y, rms: the C row without its constant NaN column) and the
     rays [8, V * P * n_pupil] (x y z L M N i opd; [8, 0] without want_rays). Forward only."""
     from . import tolerancing
-    from .raytrace import _raise_status_value
 
     if len(lens_meta) != len(ENSEMBLE_META) or len(lens) != 9:
         raise ValueError("trace_ensemble: lens holds nine tables, lens_meta ENSEMBLE_META")
@@ -1565,7 +1526,7 @@ def trace_ensemble(lens: list[torch.Tensor], lens_meta: list[int], final_thickne
         final_thickness.detach().to(torch.float64).contiguous(), seg.contiguous(),
         apod, px.detach().contiguous(), py.detach().contiguous(), bool(want_rays))
     if apod is not None:  # only an apodization record can raise a status bit here
-        _raise_status_value(int(status.item()))
+        _calls.raise_status(int(status.item()))
     if rays is None:
         rays = px.new_empty((8, 0), dtype=torch.float64)
     return stats[..., :4].contiguous(), rays

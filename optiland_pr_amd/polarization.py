@@ -6,6 +6,10 @@ registry and to_dict / from_dict keys. What a coating does to a ray and the per-
 update of the polarization matrix run in the trace kernels (csrc/ort_polar.h,
 trace_kernel<F_POL>); `PolarizedRays.update_intensity` / `get_output_field` are torch
 operations on the tensors the kernel returned, for callers who hold a PolarizedRays.
+This module calls no library entry itself: trace_pupil_polarized and
+trace_sequential_polarized build the ort_polarization struct, allocate the outputs and hand
+both to raytrace.trace_pupil_on / trace_rays_on, which trace on the lens's own library
+(raytrace.py for a DeviceLens, host.py for a HostLens).
 
 Reference behaviour kept as it is: a polarized state's intensity
 replaces the traced one (apodization, absorption and clipping are lost), an unpolarized
@@ -15,11 +19,9 @@ and a surface with a SimpleCoating does not update the polarization matrix.
 
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _abi, _calls, _native
+from . import _abi, _native
 from ._calls import addr
 from .raytrace import RealRays
 
@@ -248,37 +250,8 @@ def check_polarization(optic):
                          "polarization-dependent coatings.")
 
 
-def _bytes_tensor(arr):
-    return torch.from_numpy(np.frombuffer(np.ascontiguousarray(arr).tobytes(),
-                                          dtype=np.uint8).copy())
-
-
-def _host_launch(hl, seg, px, py, outs, n, seg_len, pupil_per_ray, rec, pol, apod):
-    """ort_host_trace_pupil_polarized: one Newton group, as host.trace_pupil. seg / apod:
-    the SEGMENT / APODIZATION records as uint8 CPU tensors (apod: or None)."""
-    from .raytrace import _raise_status_value
-
-    lib = _native.load_host()
-    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
-    status = np.zeros(1, dtype=np.int32)
-    updates = np.zeros(max(1, hl.table.n_surfaces), dtype=np.int32)
-    opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
-    out_c = _calls.rays_struct(outs)
-    rc = lib.ort_host_trace_pupil_polarized(
-        C.byref(hl.c), addr(px), addr(py), C.byref(out_c), C.byref(batch), C.byref(opt),
-        addr(rec), addr(updates), addr(status), C.byref(pol))
-    _native.check(rc, "ort_host_trace_pupil_polarized")
-    _raise_status_value(int(status[0]))
-
-
 def _coatings_of(lens):
     return lens.resident("coatings", np.ascontiguousarray(lens.table.coatings).view(np.uint8))
-
-
-def _apod_of(lens):
-    if lens.device.type != "cpu":
-        return lens.apod
-    return None if lens.table.apod is None else _bytes_tensor(lens.table.apod)
 
 
 def trace_pupil_polarized(lens, segs, px, py, n, seg_len, mode, state, pupil_per_ray=False,
@@ -300,27 +273,11 @@ def trace_pupil_polarized(lens, segs, px, py, n, seg_len, mode, state, pupil_per
     if coat is None:
         coat = _coatings_of(lens)
     if isinstance(apod, str):
-        apod = _apod_of(lens)
+        apod = lens.apod
+    # (coat, planes and apod stay referenced here until the launch is enqueued)
     pol = polarization_struct(mode, state, addr(coat), addr(planes), field)
-    if dev.type == "cpu":
-        seg = segs if torch.is_tensor(segs) else _bytes_tensor(
-            np.asarray(segs, dtype=_abi.SEGMENT))
-        _host_launch(lens, seg, px, py, outs, n, seg_len, pupil_per_ray, rec, pol, apod)
-        return outs, planes
-    lib = _native.load()
-    seg_dev = (segs if torch.is_tensor(segs) else
-               lens.resident("segments", np.asarray(segs, dtype=_abi.SEGMENT)))
-    batch = _calls.pupil_batch(n, seg_len, n, seg_dev, pupil_per_ray, apod)
-    out_c = _calls.rays_struct(outs)
-    stream = raytrace._stream_handle()
-
-    def launch(opt, stats, status):
-        rc = lib.ort_trace_pupil_polarized(
-            C.byref(lens.c), addr(px), addr(py), C.byref(out_c), C.byref(batch),
-            C.byref(opt), addr(rec), addr(stats), addr(status), C.byref(pol), stream)
-        _native.check(rc, "ort_trace_pupil_polarized")
-
-    raytrace._run(lens, launch, n, max(n, 1), list(keys), newton_mode)
+    raytrace.trace_pupil_on(lens, segs, px, py, outs, n, seg_len, pupil_per_ray, rec, keys,
+                            newton_mode, pol=pol, apod=apod)
     return outs, planes
 
 
@@ -334,33 +291,9 @@ def trace_sequential_polarized(lens, rays_in, mode, state, rec=None, want_p=True
     n = rays_in[0].numel()
     outs = [torch.empty(n, dtype=torch.float64, device=dev) for _ in range(8)]
     planes = torch.empty(18 * n, dtype=torch.float64, device=dev) if want_p else None
-    coat = _coatings_of(lens)
+    coat = _coatings_of(lens)  # (with planes: referenced until the launch is enqueued)
     pol = polarization_struct(mode, state, addr(coat), addr(planes))
-    batch = _calls.resident_batch(n)
-    in_c, out_c = _calls.rays_struct(rays_in), _calls.rays_struct(outs)
-    if dev.type == "cpu":
-        from .raytrace import _raise_status_value
-
-        lib = _native.load_host()
-        status = np.zeros(1, dtype=np.int32)
-        opt = _native.ort_options(_abi.NEWTON_SCHEDULE, int(start_surface), None)
-        rc = lib.ort_host_trace_sequential_polarized(
-            C.byref(lens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-            addr(rec), None, addr(status), C.byref(pol))
-        _native.check(rc, "ort_host_trace_sequential_polarized")
-        _raise_status_value(int(status[0]))
-        return outs, planes
-    lib = _native.load()
-    stream = raytrace._stream_handle()
-
-    def launch(opt, stats, status):
-        opt.start_surface = start_surface
-        rc = lib.ort_trace_sequential_polarized(
-            C.byref(lens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-            addr(rec), addr(stats), addr(status), C.byref(pol), stream)
-        _native.check(rc, "ort_trace_sequential_polarized")
-
-    raytrace._run(lens, launch, n, max(n, 1), [], newton_mode)
+    raytrace.trace_rays_on(lens, rays_in, outs, start_surface, rec, newton_mode, pol=pol)
     return outs, planes
 
 
@@ -421,16 +354,13 @@ def trace_optic(optic, segs, px, py, n, seg_len, wavelength, pupil_per_ray, inte
     outs, planes = trace_pupil_polarized(lens, segs, px, py, n, seg_len, mode, state,
                                          pupil_per_ray=pupil_per_ray, rec=rec,
                                          want_p=polarized, keys=keys, newton_mode=newton_mode)
-    cls = PolarizedRays if polarized else RealRays
-    out = cls.__new__(cls)
-    for a, t in zip(_abi.RAY_FIELDS, outs, strict=True):
-        setattr(out, a, t)
-    out.w = torch.full((n,), float(wavelength), dtype=torch.float64, device=dev)
-    out.is_normalized = True
+    out = (PolarizedRays if polarized else RealRays).of(
+        outs, torch.full((n,), float(wavelength), dtype=torch.float64, device=dev))
     rays0 = None
     if record or polarized:
-        rays0 = raytrace.RealRays.empty(n, 0.0, device=dev)
-        _generate(lens, segs, px, py, rays0, n, seg_len, pupil_per_ray)
+        # the generated rays themselves (the object-surface record, PolarizedRays._L0 ...)
+        rays0 = RealRays.empty(n, 0.0, device=dev)
+        raytrace.generate_rays(segs, px, py, rays0, n, seg_len, pupil_per_ray, apod=lens.apod)
     if polarized:
         out.p = planes_to_p(planes, n)
         out._i0, out._L0, out._M0, out._N0 = rays0.i, rays0.L, rays0.M, rays0.N
@@ -442,19 +372,3 @@ def trace_optic(optic, segs, px, py, n, seg_len, wavelength, pupil_per_ray, inte
     # (real_ray_tracer.py:94-95)
     raytrace._record_into(sg, rec, n, lens.table.rec_surfaces, rays0)
     return out
-
-
-def _generate(lens, segs, px, py, rays0, n, seg_len, pupil_per_ray):
-    """The generated rays themselves (the object-surface record, PolarizedRays._L0 ...)."""
-    from . import raytrace
-
-    if lens.device.type != "cpu":
-        raytrace.generate_rays(segs, px, py, rays0, n, seg_len, pupil_per_ray, apod=lens.apod)
-        return
-    seg = _bytes_tensor(np.asarray(segs, dtype=_abi.SEGMENT))
-    apod = _apod_of(lens)  # (kept alive through the call: the struct holds its address)
-    batch = _calls.pupil_batch(n, seg_len, n, seg, pupil_per_ray, apod)
-    out_c = rays0.c_struct()
-    rc = _native.load_host().ort_host_generate_rays(addr(px), addr(py), C.byref(out_c),
-                                                    C.byref(batch))
-    _native.check(rc, "ort_host_generate_rays")

@@ -22,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi, _calls, _native, autodiff
-from ._calls import addr
+from ._calls import ChebyshevRangeError, ZernikeRangeError, addr  # noqa: F401 (re-exported)
 from .pupil import pupil_arrays
 from .lowering import (LensTable, lower_apodization, lower_surface_group, pupil_scalars,
                        segment_params)
@@ -31,20 +31,6 @@ try:
     import torch
 except ImportError:  # pragma: no cover
     torch = None
-
-
-class ZernikeRangeError(ValueError):
-    pass
-
-
-class ChebyshevRangeError(ValueError):
-    pass
-
-
-_CHEBYSHEV_MSG = ("Chebyshev input coordinates must be normalized to [-1, 1]. Consider "
-                  "updating the normalization factors.")  # chebyshev.py:203-215
-_ZERNIKE_MSG = ("Zernike coordinates must be normalized to [-1, 1]. Consider updating the "
-                "normalization radius to 1.1x the surface aperture.")
 
 
 def get_device():
@@ -67,8 +53,7 @@ def _stream_handle():
 
 
 def _to_device_bytes(arr: np.ndarray, device):
-    buf = np.frombuffer(np.ascontiguousarray(arr).tobytes(), dtype=np.uint8).copy()
-    return torch.from_numpy(buf).to(device)
+    return _calls.bytes_tensor(arr).to(device)
 
 
 # --------------------------------------------------------------------------------------
@@ -99,10 +84,18 @@ class RealRays:
     @classmethod
     def empty(cls, n, wavelength, device=None):
         dev = device or get_device()
+        return cls.of([torch.empty(n, dtype=torch.float64, device=dev) for _ in range(8)],
+                      torch.full((n,), float(wavelength), dtype=torch.float64, device=dev))
+
+    @classmethod
+    def of(cls, fields, w=None):
+        """The rays of 8 existing tensors (x, y, z, L, M, N, i, opd), not copied; .w only
+        when given."""
         r = cls.__new__(cls)
-        for a in _abi.RAY_FIELDS:
-            setattr(r, a, torch.empty(n, dtype=torch.float64, device=dev))
-        r.w = torch.full((n,), float(wavelength), dtype=torch.float64, device=dev)
+        for a, t in zip(_abi.RAY_FIELDS, fields, strict=True):
+            setattr(r, a, t)
+        if w is not None:
+            r.w = w
         r.is_normalized = True
         return r
 
@@ -473,7 +466,7 @@ def check_pending(dlens: DeviceLens, block=False):
                 "the Newton schedule did not settle in the device-verified rounds "
                 f"(flag {int(flags[R])}): trace again with newton_mode='reference'")
         if p["status"]:
-            _raise_status_value(_last_status(host, R, p["fused"]))
+            _raise_status(_last_status(host, R, p["fused"]), dlens)
 
 
 def _last_status(host, R, fused):
@@ -505,7 +498,7 @@ def check_graph_flags(dlens: DeviceLens):
             "the Newton schedule did not settle in the captured device-verified rounds "
             f"(flag {int(flags[R])}): re-capture after a trace with newton_mode='reference'")
     if p["status"]:
-        _raise_status_value(_last_status(host, R, p["fused"]))
+        _raise_status(_last_status(host, R, p["fused"]), dlens)
 
 
 def check_all_pending():
@@ -693,13 +686,13 @@ def _run_protocol(dlens, launch, n_rays, group_len, keys, newton_mode, with_stat
     if not dlens.newton or n_rays == 0:
         opt = _native.ort_options(_abi.NEWTON_SCHEDULE, 0, None)
         launch(opt, None, status)
-        _raise_status(status)
+        _raise_status(status, dlens)
         return False
     if newton_mode == "wave":
         stats = torch.empty(n_groups * S * _abi.NEWTON_STAT.itemsize, dtype=torch.uint8, device=dev)
         opt = _native.ort_options(_abi.NEWTON_WAVE, 0, None)
         launch(opt, stats, status)
-        _raise_status(status)
+        _raise_status(status, dlens)
         return False
     if len(keys) != n_groups:
         keys = [("group", g) for g in range(n_groups)]
@@ -732,32 +725,21 @@ def _run_protocol(dlens, launch, n_rays, group_len, keys, newton_mode, with_stat
             dlens._dev_sched.pop(tuple(keys), None)  # re-seeded from this on device use
             dlens.last_schedule = sched
             if need_status:
-                _raise_status_value(int(host[nb:nb + 4].view(np.int32)[0]))
+                _raise_status(int(host[nb:nb + 4].view(np.int32)[0]), dlens)
             return False
         sched = new
     raise RuntimeError("Newton schedule did not settle")
 
 
-def _raise_status(status):
+def _raise_status(status, lens=None):
+    """_calls.raise_status of the status word of a launch of `lens`: an int, a one-element
+    device tensor (read here) or None (the launch kept none)."""
     if status is None:
         return
-    _raise_status_value(int(status.item()))
-
-
-def _raise_status_value(v):
-    if v & _abi.STATUS_BAD_APODIZATION:
-        raise ValueError("the apodization record holds a kind the trace core does not know")
-    if v & _abi.STATUS_BAD_GEOMETRY:
-        raise ValueError("the lens table holds a geometry id the trace core does not know "
-                         "(library / host ABI mismatch?)")
-    if v & _abi.STATUS_ZERNIKE_RANGE:
-        raise ZernikeRangeError(_ZERNIKE_MSG)
-    if v & _abi.STATUS_CHEBYSHEV_RANGE:
-        raise ChebyshevRangeError(_CHEBYSHEV_MSG)
-    if v & _abi.STATUS_SCATTER_ATTEMPTS:
-        from .scatter import ScatterAttemptsError
-
-        raise ScatterAttemptsError("BSDF scattering used up its attempts")
+    v = int(status.item()) if torch.is_tensor(status) else status
+    if v:
+        _calls.raise_status(v, getattr(lens, "table", None),
+                            getattr(lens, "scatter", (0, None))[1])
 
 
 def _scatter_call(dlens, ray_offset, tape=None, rms=None):
@@ -774,15 +756,7 @@ def _scatter_call(dlens, ray_offset, tape=None, rms=None):
     return scatter.scatter_struct(dlens, ray_offset)
 
 
-def _run_scatter(dlens, scat, *args, **kw):
-    """_run, with a used-up rejection loop reported by surface and sigma."""
-    from . import scatter
-
-    try:
-        _run(dlens, *args, **kw)
-    except scatter.ScatterAttemptsError:
-        raise scatter.attempts_error(scatter.describe(dlens.table), scat[0].max_attempts) \
-            from None
+_LENS_APOD = object()  # trace_pupil's apod default: the lens's own record
 
 
 def upload_segments(segments: np.ndarray, device):
@@ -793,24 +767,26 @@ def upload_segments(segments: np.ndarray, device):
 def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
                 seg_len, group_len, pupil_per_ray=False, keys=(), rec=None,
                 newton_mode="reference", start_surface=0, tape=None, exact_only=False, rms=None,
-                ray_offset=0):
+                ray_offset=0, pol=None, apod=_LENS_APOD):
     """Generate + trace in one launch (ort_trace_pupil; ort_trace_pupil_scatter for a lens
-    with BSDF surfaces, whose ray r draws as ray r + ray_offset). `segments` is a host SEGMENT array
+    with BSDF surfaces, whose ray r draws as ray r + ray_offset; ort_trace_pupil_polarized
+    with `pol`, the ort_polarization of a lens lowered with polarized=True, whose caller
+    keeps its coatings and planes alive). `segments` is a host SEGMENT array
     or the device tensor returned by upload_segments (no per-call copy). tape: a device
     buffer of ort_vjp_tape_size bytes the launch writes the adjoint tape into (Newton
     lenses; the backward then runs the reverse sweep only). rms: (rms [], stats [5]) device
     tensors that receive RayOperand.rms_spot_size of the final points: the taped kernel's
     epilogue writes its workgroup rows (ort_options.rms_part), combined by the second
     workgroup of the device rounds' finish launch (ort_newton_finish_rms) or by one
-    ort_rms_finish launch (needs the tape and one wavelength)."""
+    ort_rms_finish launch (needs the tape and one wavelength). apod: an APODIZATION record
+    on the device (or None) instead of the lens's own."""
     lib = _native.load()
-    seg_dev = (segments if torch.is_tensor(segments) else
-               dlens.resident("segments", np.asarray(segments, dtype=_abi.SEGMENT)))
-    batch = _calls.pupil_batch(n_rays, seg_len, group_len, seg_dev, pupil_per_ray, dlens.apod)
+    seg_dev = _calls.segments_of(dlens, segments)
+    batch = _calls.pupil_batch(n_rays, seg_len, group_len, seg_dev, pupil_per_ray,
+                               dlens.apod if apod is _LENS_APOD else apod)
     out_c = out.c_struct()
     stream = _stream_handle()  # one stream for all the launches of this call
-    args = (C.byref(dlens.c), addr(px), addr(py), C.byref(out_c), C.byref(batch))
-    rec_p, tape_p = addr(rec), addr(tape)
+    tape_p = addr(tape)
     rows = -(-int(n_rays) // 256)  # one row per trace workgroup (kBlock)
     part = None
     if rms is not None:
@@ -818,7 +794,9 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
             raise ValueError("trace_pupil: the fused rms spot size needs the taped forward")
         part = torch.empty(rows * 4, dtype=torch.float64, device=dlens.device)
     part_p = addr(part)
-    scat = _scatter_call(dlens, ray_offset, tape, rms)
+    scat = _scatter_call(dlens, ray_offset, tape, rms)  # (struct, its records: kept alive)
+    entry, extra = _calls.forward_entry("device", "pupil", pol, scat and scat[0])
+    src = (px, py)
 
     def launch(opt, stats, status):
         opt.start_surface = start_surface
@@ -826,17 +804,8 @@ def trace_pupil(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays,
         opt.rms_part = part_p
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
-        if scat is not None:
-            rc = lib.ort_trace_pupil_scatter(*args, C.byref(opt), rec_p, addr(stats),
-                                             addr(status), C.byref(scat[0]), stream)
-            _native.check(rc, "ort_trace_pupil_scatter")
-            return
-        rc = lib.ort_trace_pupil(*args, C.byref(opt), rec_p, addr(stats), addr(status), stream)
-        _native.check(rc, "ort_trace_pupil")
-
-    if scat is not None:
-        _run_scatter(dlens, scat, launch, n_rays, group_len, list(keys), newton_mode)
-        return seg_dev
+        _calls.call_forward(lib, entry, dlens.c, src, out_c, batch, opt, rec, stats, status,
+                            extra, stream)
 
     _run(dlens, launch, n_rays, group_len, list(keys), newton_mode,
          rms=(part, rows, rms[1], rms[0]) if rms is not None and n_rays > 0 else None)
@@ -856,8 +825,7 @@ def trace_spot(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays, seg_l
         trace_pupil(dlens, segments, px, py, out, n_rays, seg_len, seg_len)
         return spot.run(out)
     lib = _native.load()
-    seg_dev = (segments if torch.is_tensor(segments) else
-               dlens.resident("segments", np.asarray(segments, dtype=_abi.SEGMENT)))
+    seg_dev = _calls.segments_of(dlens, segments)
     batch = _calls.pupil_batch(n_rays, seg_len, seg_len, seg_dev, False, dlens.apod)
     out_c = out.c_struct()
 
@@ -874,9 +842,10 @@ def trace_spot(dlens: DeviceLens, segments, px, py, out: RealRays, n_rays, seg_l
 
 def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_len=None,
                keys=(), rec=None, newton_mode="reference", start_surface=0, segments=None,
-               seg_len=None, per_ray_w=False, exact_only=False, ray_offset=0):
+               seg_len=None, per_ray_w=False, exact_only=False, ray_offset=0, pol=None):
     """Trace resident rays (ort_trace_sequential; ort_trace_sequential_scatter for a lens
-    with BSDF surfaces, whose ray r draws as ray r + ray_offset); rays_out may be rays_in
+    with BSDF surfaces, whose ray r draws as ray r + ray_offset;
+    ort_trace_sequential_polarized with `pol`, as trace_pupil); rays_out may be rays_in
     (in place).
     per_ray_w: n and k per ray from rays_in.w (the lens's material tables) instead of
     the per-wavelength tables. exact_only: ORT_OPT_EXACT (no deferred-check pass; the same
@@ -892,50 +861,74 @@ def trace_rays(dlens: DeviceLens, rays_in: RealRays, rays_out: RealRays, group_l
                                             validate=True)
         batch.w = addr(w_keep)
     in_c, out_c = rays_in.c_struct(), rays_out.c_struct()
-    scat = _scatter_call(dlens, ray_offset)
+    scat = _scatter_call(dlens, ray_offset)  # (struct, its records: kept alive)
     if scat is not None and per_ray_w:
         raise ValueError("BSDF surfaces trace one wavelength per call")
+    entry, extra = _calls.forward_entry("device", "sequential", pol, scat and scat[0])
+    stream = _stream_handle()  # one stream for all the launches of this call
 
     def launch(opt, stats, status):
         opt.start_surface = start_surface
         if exact_only:
             opt.flags |= _abi.OPT_EXACT
-        if scat is not None:
-            rc = lib.ort_trace_sequential_scatter(
-                C.byref(dlens.c), C.byref(in_c), C.byref(out_c), C.byref(batch), C.byref(opt),
-                addr(rec), addr(stats), addr(status), C.byref(scat[0]), _stream_handle())
-            _native.check(rc, "ort_trace_sequential_scatter")
-            return
-        rc = lib.ort_trace_sequential(C.byref(dlens.c), C.byref(in_c), C.byref(out_c),
-                                      C.byref(batch), C.byref(opt), addr(rec), addr(stats),
-                                      addr(status), _stream_handle())
-        _native.check(rc, "ort_trace_sequential")
+        _calls.call_forward(lib, entry, dlens.c, in_c, out_c, batch, opt, rec, stats, status,
+                            extra, stream)
 
     if rays_in is rays_out and dlens.newton and newton_mode != "wave":
         # a schedule miss re-runs the launch: keep the input
-        src = RealRays.__new__(RealRays)
-        for a in (*_abi.RAY_FIELDS, "w"):
-            setattr(src, a, getattr(rays_in, a).clone())
+        src = RealRays.of([getattr(rays_in, a).clone() for a in _abi.RAY_FIELDS],
+                          rays_in.w.clone())
         in_c = src.c_struct()
-    if scat is not None:
-        _run_scatter(dlens, scat, launch, n, group_len, list(keys), newton_mode)
-    else:
-        _run(dlens, launch, n, group_len, list(keys), newton_mode)
+    _run(dlens, launch, n, group_len, list(keys), newton_mode)
     del w_keep  # (the launches above are ordered on the stream before any reuse)
     return seg_dev
 
 
+def trace_pupil_on(lens, segs, px, py, outs, n, seg_len, pupil_per_ray=False, rec=None, keys=(),
+                   newton_mode="reference", ray_offset=0, pol=None, apod=_LENS_APOD):
+    """Generate and trace into `outs` (8 tensors) as one Newton group on the lens's own
+    library: host.trace_pupil for a HostLens, trace_pupil for a DeviceLens. With
+    trace_rays_on the one dispatch on the lens's device, for the callers that serve both
+    (polarization.py, the forward-only ops)."""
+    if lens.device.type == "cpu":
+        from . import host
+
+        host.trace_pupil(lens, segs, px, py, n, seg_len, pupil_per_ray,
+                         lens.apod if apod is _LENS_APOD else apod, ray_offset, rec, pol, outs)
+    else:
+        trace_pupil(lens, segs, px, py, RealRays.of(outs), n, seg_len, max(n, 1),
+                    pupil_per_ray, keys, rec, newton_mode, ray_offset=ray_offset, pol=pol,
+                    apod=apod)
+
+
+def trace_rays_on(lens, rays_in, outs, start_surface=0, rec=None, newton_mode="reference",
+                  ray_offset=0, pol=None):
+    """Trace resident rays (8 tensors, one wavelength) into `outs` on the lens's own
+    library: host.trace_sequential or trace_rays (see trace_pupil_on)."""
+    if lens.device.type == "cpu":
+        from . import host
+
+        host.trace_sequential(lens, rays_in, None, False, start_surface, rec, ray_offset, pol,
+                              outs)
+    else:
+        trace_rays(lens, RealRays.of(rays_in), RealRays.of(outs), rec=rec,
+                   newton_mode=newton_mode, start_surface=start_surface,
+                   ray_offset=ray_offset, pol=pol)
+
+
 def generate_rays(segments, px, py, out: RealRays, n_rays, seg_len, pupil_per_ray=False,
                   apod=None):
-    """Ray generation only (ort_generate_rays). apod: a device APODIZATION record
-    (DeviceLens.apod) or None."""
-    lib = _native.load()
-    seg_dev = _to_device_bytes(segments, out.x.device)
+    """Ray generation only (ort_generate_rays; ort_host_generate_rays for CPU outputs).
+    apod: an APODIZATION record on the outputs' device (DeviceLens.apod / HostLens.apod) or
+    None."""
+    dev = out.x.device
+    seg_dev = _to_device_bytes(np.asarray(segments, dtype=_abi.SEGMENT), dev)
     batch = _calls.pupil_batch(n_rays, seg_len, n_rays, seg_dev, pupil_per_ray, apod)
     out_c = out.c_struct()
-    rc = lib.ort_generate_rays(addr(px), addr(py), C.byref(out_c), C.byref(batch),
-                               _stream_handle())
-    _native.check(rc, "ort_generate_rays")
+    if dev.type == "cpu":
+        _calls.call_generate(_native.load_host(), "host", px, py, out_c, batch)
+    else:
+        _calls.call_generate(_native.load(), "device", px, py, out_c, batch, _stream_handle())
     return seg_dev
 
 
@@ -1135,7 +1128,7 @@ class RealRayTracer:
         if float(dlens.table.final_thickness) != 0.0:
             raise NotImplementedError("differentiable trace with a non-zero image-space "
                                       "thickness (last surface) is not supported")
-        seg_dev = dlens.resident("segments", np.asarray(segs, dtype=_abi.SEGMENT))
+        seg_dev = _calls.segments_of(dlens, segs)
         if record_all:  # non-differentiable records of every surface first
             rec = torch.empty(dlens.table.n_rec * 8 * n, dtype=torch.float64, device=dlens.device)
             tmp = RealRays.empty(n, wavelength, device=dlens.device)
@@ -1152,12 +1145,7 @@ class RealRayTracer:
                                          wavelength, keys, newton_mode, want_rms=want_rms)
         if want_rms and outs[8].dim() == 0:  # the trace took it (the taped single-λ path)
             RMS_REQUEST["rms"] = outs[8]
-        outs = outs[:8]
-        out = RealRays.__new__(RealRays)
-        for a, t in zip(_abi.RAY_FIELDS, outs, strict=True):
-            setattr(out, a, t)
-        out.w = w
-        out.is_normalized = True
+        out = RealRays.of(outs[:8], w)
         sg = self.optic.surface_group
         if not record_all:
             sg.reset()
@@ -1213,9 +1201,8 @@ def trace_surface_group(sg, rays: RealRays, skip=0, newton_mode="reference"):
         rec = torch.empty(table.n_rec * 8 * n, dtype=torch.float64, device=rays.x.device)
     rays0 = None
     if rec is not None:
-        rays0 = RealRays.__new__(RealRays)
-        for a in (*_abi.RAY_FIELDS, "w"):
-            setattr(rays0, a, getattr(rays, a).clone())
+        rays0 = RealRays.of([getattr(rays, a).clone() for a in _abi.RAY_FIELDS],
+                            rays.w.clone())
     trace_rays(dlens, rays, rays, rec=rec, newton_mode=newton_mode,
                start_surface=max(int(skip) - 1, 0), per_ray_w=per_ray)
     if rec is not None:
@@ -1256,10 +1243,7 @@ def _trace_surface_group_polarized(sg, rays, skip):
         lens, rays_in, mode, None, rec=rec, want_p=polarized,
         start_surface=max(int(skip) - 1, 0))
     if rec is not None:
-        rays0 = RealRays.__new__(RealRays)
-        for a, t in zip(_abi.RAY_FIELDS, rays_in, strict=True):
-            setattr(rays0, a, t)
-        _record_into(sg, rec, n, table.rec_surfaces, rays0)
+        _record_into(sg, rec, n, table.rec_surfaces, RealRays.of(rays_in))
     for a, t in zip(_abi.RAY_FIELDS, outs, strict=True):
         setattr(rays, a, t)
     if polarized:

@@ -270,9 +270,8 @@ def _pupil_points(distribution, num_rays):
             np.ascontiguousarray(d.y, dtype=np.float64))
 
 
-def _bytes_tensor(a):
-    return torch.from_numpy(np.frombuffer(np.ascontiguousarray(a).tobytes(),
-                                          dtype=np.uint8).copy())
+# (the name tests/test_gpu_ensemble.py and tools/ensemble_rate.py upload their segments with)
+_bytes_tensor = _calls.bytes_tensor
 
 
 def image_points_host(optic, surface_number, Hx, Hy, num_rays, wavelength,
@@ -287,9 +286,9 @@ def image_points_host(optic, surface_number, Hx, Hy, num_rays, wavelength,
     table = lower_surface_group(optic.surface_group, [wavelength])
     table.apod = lower_apodization(optic)
     EPL, EPD = pupil_scalars(optic)
-    seg = _bytes_tensor(np.stack([segment_params(optic, float(Hx), float(Hy), 0, EPL, EPD)]))
+    seg = _calls.bytes_tensor(np.stack([segment_params(optic, float(Hx), float(Hy), 0, EPL, EPD)]))
     px, py = (torch.from_numpy(v) for v in _pupil_points(distribution, num_rays))
-    apod = None if table.apod is None else _bytes_tensor(table.apod)
+    apod = None if table.apod is None else _calls.bytes_tensor(table.apod)
     n = px.numel()
     outs, _ = host.trace_pupil(host.HostLens(table), seg, px, py, n, n, False, apod=apod)
     return outs[0], outs[1]
@@ -433,7 +432,7 @@ class EnsembleTable:
         """The nine tables in DeviceLens.lens_tensors' order (structured ones as bytes) and
         final_thickness [V], on `device`."""
         def up(a):
-            return (_bytes_tensor(a) if a.dtype.fields else
+            return (_calls.bytes_tensor(a) if a.dtype.fields else
                     torch.from_numpy(np.ascontiguousarray(a).reshape(-1).copy())).to(device)
 
         lens = [up(a) for a in (self.surfaces, self.cs_ops, self.coef, self.zern, self.n_tab,
@@ -595,9 +594,9 @@ class Tolerancing:
                     ens, segs = stacked[key]
                     px, py = (torch.from_numpy(v).to(dev) for v in _pupil_points(key[1], key[0]))
                     lens, ft = ens.tensors(dev)
-                    apod = None if ens.apod is None else _bytes_tensor(ens.apod).to(dev)
+                    apod = None if ens.apod is None else _calls.bytes_tensor(ens.apod).to(dev)
                     stats = torch.ops.ort.trace_ensemble(
-                        lens, ens.meta(len(g["pairs"])), ft, _bytes_tensor(segs).to(dev), apod,
+                        lens, ens.meta(len(g["pairs"])), ft, _calls.bytes_tensor(segs).to(dev), apod,
                         px, py, False)[0]
                     results.append((g, stats))
                 for g, stats in results:  # one read-back per launch, after every launch
