@@ -51,16 +51,35 @@ using ::exp;
 using ::fabs;
 using ::sin;
 
-// IEEE sqrt. gfx950 lowers a correctly rounded fp64 sqrt to v_rsq_f64 and two Goldschmidt
-// / Newton refinements wrapped in an input scaling (x < 2^-767) and a zero / +inf class
-// fix-up. For 2^-767 <= x < inf the wrappers are identities, so that range runs the
-// refinement alone -- the same instructions on the same values, bit-identical to sqrt(x)
-// -- and every other input (0, tiny, inf, NaN, negative) takes the full sequence.
-ORT_INLINE double sqrt(double x) {
+// ---------------------------------------------------------------------------------
+// The gfx950 fp64 sequences every stored bit rests on, each written once: the bare
+// instructions, no range test, no flag. sqrt / shared_div / sdiv below add the per-operation
+// fallback, ort_fastpath.h's wrappers the deferred range flag. Host arms (here only): plain
+// IEEE operations; seeds, reciprocals and h are unused there and 0.
+// ---------------------------------------------------------------------------------
+ORT_INLINE double rsq_seed(double x) {  // v_rsq_f64: (1 + e0) / sqrt(x), e0 <= 2^-20
 #if defined(__HIP_DEVICE_COMPILE__)
-  // the refinement runs unconditionally (no data-dependent branch around the common
-  // case); the rare out-of-range lanes redo it with the full sequence
-  const double y = __builtin_amdgcn_rsq(x);
+  return __builtin_amdgcn_rsq(x);
+#else
+  (void)x;
+  return 0.0;
+#endif
+}
+
+// The Goldschmidt square root from a seed y = (1 + e0) / sqrt(x) (v_rsq's, rsq_seed, or a
+// caller's own, who states where its bound on e0 comes from): g = x y, h = y / 2, one
+// coupled step r = 1/2 - h g, g += g r, h += h r, then two residual corrections of g. With
+// y = (1 + e0) / sqrt(x): r = 1/2 - (1 + e0)^2 / 2 = -e0 - e0^2 / 2, so the refined h =
+// (1 + e0)(1 - e0 - e0^2 / 2) / (2 sqrt(x)) = (1 - 1.5 e0^2 + O(e0^3)) / (2 sqrt(x)) up to
+// three roundings (2^-52 relative together). That h is handed out: 2 h is a reciprocal of
+// the returned root g (g is sqrt(x) rounded: 2^-53 more) with relative error |eh| <=
+// 1.5 e0^2 + 2^-51, a seed for rcp_seeded below. The coupled step squares the seed's error
+// whatever produced it, so the bounds hold for any seed with |e0| <= 2^-20. For
+// 2^-767 <= x < inf and v_rsq's seed these are gfx950's own instructions for a correctly
+// rounded sqrt(x) (its input scaling and zero / +inf fix-up are identities there). A NaN
+// seed gives a NaN root.
+ORT_INLINE double sqrt_seeded_h(double x, double y, double& h_out) {
+#if defined(__HIP_DEVICE_COMPILE__)
   double g = x * y;
   double h = y * 0.5;
   const double r = fma(-h, g, 0.5);
@@ -70,11 +89,94 @@ ORT_INLINE double sqrt(double x) {
   g = fma(d, h, g);
   d = fma(-g, g, x);
   g = fma(d, h, g);
-  if (__builtin_expect(!(x >= 0x1p-767 && x < __builtin_inf()), 0)) g = ::sqrt(x);
+  h_out = h;
   return g;
 #else
+  (void)y;
+  h_out = 0.0;
   return ::sqrt(x);
 #endif
+}
+
+// 1 / b from v_rcp_f64 (relative error e1) and two Newton steps: e1^2 after the first,
+// e1^4 after the second
+ORT_INLINE double rcp_refined(double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double y = __builtin_amdgcn_rcp(b);
+  double e = fma(-b, y, 1.0);
+  y = fma(y, e, y);
+  e = fma(-b, y, 1.0);
+  y = fma(y, e, y);
+  return y;
+#else
+  (void)b;
+  return 0.0;
+#endif
+}
+
+// 1 / b from a seed y0 = (1 + es) / b instead of v_rcp(b): ONE Newton step
+// e = fma(-b, y0, 1) = -es (exact up to its rounding), y = fma(y0, e, y0) = (1 - es^2) / b
+// rounded. A seed with |es| <= 1.5 e0^2 + 2^-51 (sqrt_seeded_h's 2 h) stands where
+// rcp_refined's first step ends, and the one step lands at es^2 ~ 2.25 e0^4 -- for
+// e0 <= 2^-20 under 2^-78, far below the 2^-53 of y's own rounding, as e1^4 is. The
+// quotient sequence then rounds the same real a / b from a reciprocal of the same accuracy.
+// A non-finite or zero seed (x = 0, inf or NaN under the root) gives a NaN reciprocal and
+// NaN quotients where v_rcp gave inf / 0 / NaN: non-finite either way.
+ORT_INLINE double rcp_seeded(double b, double y0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double e = fma(-b, y0, 1.0);
+  return fma(y0, e, y0);
+#else
+  (void)b;
+  (void)y0;
+  return 0.0;
+#endif
+}
+
+// a / b from y = 1 / b (rcp_refined, rcp_seeded): q0 = a y, r = fma(-b, q0, a),
+// q = fma(r, y, q0), the IEEE quotient inside the exponent range where gfx950's
+// v_div_scale / v_div_fixup are identities (SharedDiv below). An exact-zero numerator
+// gives +0 * sign(b): q0 carries the sign, r = +0.
+ORT_INLINE double quot(double a, double b, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double q0 = a * y;
+  const double r = fma(-b, q0, a);
+  return fma(r, y, q0);
+#else
+  (void)y;
+  return a / b;
+#endif
+}
+
+// The same quotient for a divisor known to be > 0 with the residual formed negated:
+// rn = fma(b, q0, -a) = -r exactly, and fma(-rn, y, q0) rounds q0 + r y exactly as
+// fma(r, y, q0) does, but an exact-zero numerator keeps its sign (+-0 / b = +-0): for
+// a = -0, rn = (-0) + (+0) = +0 and (-rn) y + q0 = (-0) + (-0) = -0, where the plain
+// form's r = +0 turns -0 / b into +0. The negations are free operand modifiers. (For
+// b < 0 the plain form is the one that is right for both zeros.)
+ORT_INLINE double quot_pos(double a, double b, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double q0 = a * y;
+  const double rn = fma(b, q0, -a);
+  return fma(-rn, y, q0);
+#else
+  (void)y;
+  return a / b;
+#endif
+}
+
+// IEEE sqrt. gfx950 lowers a correctly rounded fp64 sqrt to v_rsq_f64 and two Goldschmidt
+// / Newton refinements wrapped in an input scaling (x < 2^-767) and a zero / +inf class
+// fix-up. For 2^-767 <= x < inf the wrappers are identities, so that range runs the
+// refinement alone -- the same instructions on the same values, bit-identical to sqrt(x)
+// -- and every other input (0, tiny, inf, NaN, negative) takes the full sequence. The
+// refinement runs unconditionally (no data-dependent branch around the common case); the
+// rare out-of-range lanes redo it with the full sequence.
+ORT_INLINE double sqrt(double x) {
+  double h;
+  double g = sqrt_seeded_h(x, rsq_seed(x), h);
+  if (__builtin_expect(!(x >= 0x1p-767 && x < __builtin_inf()), 0)) g = ::sqrt(x);
+  return g;
 }
 
 ORT_INLINE double vv(double x) { return x; }
@@ -280,31 +382,15 @@ ORT_INLINE bool div_range_ok(double v) {
 ORT_INLINE SharedDiv shared_div(double b) {
   SharedDiv d;
   d.b = b;
-#if defined(__HIP_DEVICE_COMPILE__)
   d.ok = div_range_ok(b);
-  double y = __builtin_amdgcn_rcp(b);
-  double e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  d.y = y;
-#else
-  d.ok = false;
-  d.y = 0.0;
-#endif
+  d.y = rcp_refined(b);
   return d;
 }
 
 ORT_INLINE double sdiv(double a, const SharedDiv& d) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double q0 = a * d.y;
-  const double r = fma(-d.b, q0, a);
-  double q = fma(r, d.y, q0);
+  double q = quot(a, d.b, d.y);
   if (__builtin_expect(!(d.ok && div_range_ok(a)), 0)) q = a / d.b;
   return q;
-#else
-  return a / d.b;
-#endif
 }
 
 // Quotients that only enter derivatives (the adjoint's reverse sweep and its local jets,

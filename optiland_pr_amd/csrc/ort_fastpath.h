@@ -29,12 +29,16 @@
 // wrongly rounded result) and the divisors' upper bound (a reciprocal small enough to
 // underflow a quotient) stay per operation.
 //
+// The sequences themselves (the root from a seed, the two reciprocals, the two quotients)
+// are ort_core.h's, written once there with their error bounds and host arms; each wrapper
+// here is one of them, its seed, and at most one range test.
+//
 // The plain form's kernels (F_PLAIN, fast pass only) take three shorter forms where a value
 // is already at hand or a test cannot fire on a finite result: a sphere's norm root
 // sqrt(dfdx^2 + dfdy^2 + 1) seeded from g = sqrt(1 - q) instead of v_rsq (normal_conic_rcp,
 // sqrt_seeded_h), a sphere's 1 / (L^2 + M^2 + N^2) from 2 - a and one step
-// (shared_div_unit), and sqrt(1.0 - v) without its lower-bound test (sqrt_1m). Two more
-// drop work the stored bits do not need: a sphere's quadratic keeps the one root the
+// (shared_div_unit), and sqrt(1.0 - v) without its lower-bound test (sqrt_untested). Two
+// more drop work the stored bits do not need: a sphere's quadratic keeps the one root the
 // reference would choose, predicted by a sign and held to it by a guard
 // (distance_conic_folded), and the refraction puts the normal's alignment on one sign bit
 // (refract). The Newton kernels' calls (template defaults) compile to what they did.
@@ -77,37 +81,15 @@ ORT_INLINE bool is_pos_zero(double v) {
 #endif
 }
 
-// The square roots below are ort_core.h's Goldschmidt sequence: y = v_rsq(x) with relative
-// error e0, g = x y, h = y / 2, one coupled step r = 1/2 - h g, g += g r, h += h r, then two
-// residual corrections of g. With y = (1 + e0) / sqrt(x): r = 1/2 - (1 + e0)^2 / 2 =
-// -e0 - e0^2 / 2, so the refined h = (1 + e0)(1 - e0 - e0^2 / 2) / (2 sqrt(x)) =
-// (1 - 1.5 e0^2 + O(e0^3)) / (2 sqrt(x)) up to three roundings (2^-52 relative together).
-// The *_h forms hand that h out: 2 h is a reciprocal of the returned root g (g is sqrt(x)
-// rounded: 2^-53 more) with relative error |eh| <= 1.5 e0^2 + 2^-51, the seed of
-// shared_div_seeded below. The root itself is computed exactly as before.
+// ---- square roots: ort_core.h's sqrt_seeded_h, which also hands out h (2 h ~ 1 / root, the
+// seed of shared_div_seeded below); non-finite results are left to state_ok ---------------
 
-// sqrt(x) for 2^-767 <= x < inf (ort_core.h sqrt); h: see above (host: unused, 0)
+// sqrt(x) for 2^-767 <= x < inf (ort_core.h sqrt)
 template <class B>
 ORT_INLINE double sqrt_h(double x, B& bad, double& h_out) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y;
-  double h = y * 0.5;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
+  const double g = sqrt_seeded_h(x, rsq_seed(x), h_out);
   ORT_CHK(bad, !(x >= 0x1p-767));  // +inf gives NaN: left to state_ok
-  h_out = h;
   return g;
-#else
-  (void)bad;
-  h_out = 0.0;
-  return ::sqrt(x);
-#endif
 }
 template <class B>
 ORT_INLINE double sqrt(double x, B& bad) {
@@ -115,218 +97,78 @@ ORT_INLINE double sqrt(double x, B& bad) {
   return sqrt_h(x, bad, h);
 }
 
-// sqrt(x) where x >= 1 unless NaN (sums of squares plus 1): only the upper bound could
-// fail, and +inf / NaN give NaN, which state_ok catches: no test
-template <class B>
-ORT_INLINE double sqrt_ge1_h(double x, B& bad, double& h_out) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y;
-  double h = y * 0.5;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  (void)bad;
-  h_out = h;
-  return g;
-#else
-  (void)bad;
-  h_out = 0.0;
-  return ::sqrt(x);
-#endif
+// sqrt_h without its test, for an x that cannot lie in (0, 2^-767), where the test fires
+// on a finite result. Two kinds of caller:
+//   x >= 1 unless NaN (sums of squares plus 1): only the upper bound could fail, and
+//     +inf / NaN give NaN, which state_ok catches;
+//   x = fl(1.0 - v) (the plain form's kernels): it is <= 0 or >= 2^-53 (v <= 1 - 2^-53
+//     leaves 1 - v >= 2^-53); x = 0 (rsq = inf, g = 0 inf), x < 0, NaN and +inf (v = -inf)
+//     all give NaN, which is sticky in the ray state and caught by state_ok.
+ORT_INLINE double sqrt_untested_h(double x, double& h_out) {
+  return sqrt_seeded_h(x, rsq_seed(x), h_out);
 }
-template <class B>
-ORT_INLINE double sqrt_ge1(double x, B& bad) {
+ORT_INLINE double sqrt_untested(double x) {
   double h;
-  return sqrt_ge1_h(x, bad, h);
+  return sqrt_untested_h(x, h);
 }
+// (A seed of the caller's own in v_rsq's place: sqrt_seeded_h itself, no test either;
+// normal_conic_rcp's sphere branch states where its seed's bound comes from.)
 
-// sqrt_ge1_h from a seed y = (1 + es) / sqrt(x) in v_rsq's place, |es| <= e0: the rest of
-// the sequence as it is, so the bounds above hold with es for e0 (the coupled step squares
-// the seed's error whatever produced it: |eh| <= 1.5 es^2 + 2^-51 for the returned h). The
-// caller states where its seed's bound comes from (normal_conic_rcp's sphere branch). A
-// NaN seed gives a NaN root, for state_ok. No test, as sqrt_ge1_h.
-ORT_INLINE double sqrt_seeded_h(double x, double y, double& h_out) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  double g = x * y;
-  double h = y * 0.5;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  h_out = h;
-  return g;
-#else
-  (void)y;
-  h_out = 0.0;
-  return ::sqrt(x);
-#endif
-}
-
-// sqrt(1.0 - v) for the plain form's kernels: sqrt_h without its test. x = fl(1 - v) is
-// <= 0 or >= 2^-53 (v <= 1 - 2^-53 leaves 1 - v >= 2^-53), never in (0, 2^-767) where the
-// test fires on a finite result; x = 0 (rsq = inf, g = 0 inf), x < 0, NaN and +inf
-// (v = -inf) all give NaN, which is sticky in the ray state and caught by state_ok.
-ORT_INLINE double sqrt_1m_h(double x, double& h_out) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return sqrt_seeded_h(x, __builtin_amdgcn_rsq(x), h_out);
-#else
-  h_out = 0.0;
-  return ::sqrt(x);
-#endif
-}
-ORT_INLINE double sqrt_1m(double x) {
-  double h;
-  return sqrt_1m_h(x, h);
-}
+// ---- reciprocals: ort_core.h's rcp_refined / rcp_seeded with the divisor kept beside them
+struct Div {
+  double b, y;
+};
 
 template <class B>
-ORT_INLINE SharedDiv shared_div(double b, B& bad) {
-  SharedDiv d;
-  d.b = b;
-  d.ok = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-  double y = __builtin_amdgcn_rcp(b);
-  double e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  d.y = y;
+ORT_INLINE Div shared_div(double b, B& bad) {
+  const Div d{b, rcp_refined(b)};
   // |b| <= 2^300 (false for NaN). Below 2^-1021 (zero and subnormal divisors included)
   // the reciprocal is infinite and every quotient non-finite -- NaN for a zero
   // numerator, +-inf or NaN otherwise -- which state_ok catches; in between the
   // refined reciprocal is accurate and, as every numerator is >= 2^-300 or an exact zero
   // (sdiv / sdiv0 / num_ok), q0 = a y cannot underflow (|q| >= 2^-600).
   ORT_CHK(bad, !(::fabs(b) <= 0x1p300));
-#else
-  (void)bad;
-  d.y = 0.0;
-#endif
   return d;
 }
 
-// the divisor is known to lie in [1, inf) unless NaN (a norm of (., ., 1))
-// (no test: the divisor is a norm sqrt(s), s = a^2 + b^2 + 1 >= 1, so it is at most
-// sqrt(DBL_MAX) < 2^512 -- its refined reciprocal >= 2^-512 is accurate and the quotients
-// of the checked numerators (|a| >= 2^-300 or +-0, and -1) stay normal -- or, with s
-// overflowed, +inf, whose zero reciprocal makes every quotient NaN for state_ok; NaN
-// likewise. Round 6: the b <= 2^300 test this had was one of those that cannot fail on a
-// finite result.)
-template <class B>
-ORT_INLINE SharedDiv shared_div_ge1(double b, B& bad) {
-  SharedDiv d;
-  d.b = b;
-  d.ok = true;
-  (void)bad;
-#if defined(__HIP_DEVICE_COMPILE__)
-  double y = __builtin_amdgcn_rcp(b);
-  double e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-b, y, 1.0);
-  y = fma(y, e, y);
-  d.y = y;
-#else
-  (void)bad;
-  d.y = 0.0;
-#endif
-  return d;
-}
+// shared_div without its test, for a divisor whose range is known another way:
+//   a norm sqrt(s), s = a^2 + b^2 + 1 >= 1 unless NaN: it is at most sqrt(DBL_MAX) < 2^512
+//     -- its refined reciprocal >= 2^-512 is accurate and the quotients of the checked
+//     numerators (|a| >= 2^-300 or +-0, and -1) stay normal -- or, with s overflowed, +inf,
+//     whose zero reciprocal makes every quotient NaN for state_ok; NaN likewise. (Round 6:
+//     the b <= 2^300 test this had was one of those that cannot fail on a finite result.)
+//   the Newton aspheres' positive divisors R^2, |R| (1 + q), |R| q: tested once per
+//     evaluation (lens_range below).
+ORT_INLINE Div shared_div_untested(double b) { return Div{b, rcp_refined(b)}; }
 
-// shared_div / shared_div_ge1 from a seed y0 = (1 + es) / b instead of v_rcp(b): ONE Newton
-// step e = fma(-b, y0, 1) = -es (exact up to its rounding), y = fma(y0, e, y0) =
-// (1 - es^2) / b rounded. v_rcp's own error e1 leaves the unseeded forms at e1^2 after their
-// first step and e1^4 after the second; a seed with |es| <= 1.5 e0^2 + 2^-51 (sqrt_h's
-// 2 h) stands where that first step ends, and the one step lands at es^2 ~ 2.25 e0^4 --
-// for e0 <= 2^-20 under 2^-78, far below the 2^-53 of y's own rounding, as e1^4 is. The
-// quotient sequence then rounds the same real a / b from a reciprocal of the same
-// accuracy. Range tests: the unseeded forms', unchanged.
-// A non-finite or zero seed (x = 0, inf or NaN under the root) gives a NaN reciprocal and
-// NaN quotients where v_rcp gave inf / 0 / NaN: non-finite either way, for state_ok.
+// shared_div from a seed y0 = (1 + es) / b (rcp_seeded: es^2 after its one step); the
+// range test is the unseeded form's, unchanged. A non-finite or zero seed gives NaN
+// quotients, for state_ok.
 template <class B>
-ORT_INLINE SharedDiv shared_div_seeded(double b, double y0, B& bad) {
-  SharedDiv d;
-  d.b = b;
-  d.ok = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double e = fma(-b, y0, 1.0);
-  d.y = fma(y0, e, y0);
-  ORT_CHK(bad, !(::fabs(b) <= 0x1p300));  // as shared_div
-#else
-  (void)bad;
-  (void)y0;
-  d.y = 0.0;
-#endif
+ORT_INLINE Div shared_div_seeded(double b, double y0, B& bad) {
+  const Div d{b, rcp_seeded(b, y0)};
+  ORT_CHK(bad, !(::fabs(b) <= 0x1p300));
   return d;
 }
-// divisor in [1, inf) unless NaN: no test (shared_div_ge1)
-ORT_INLINE SharedDiv shared_div_ge1_seeded(double b, double y0) {
-  SharedDiv d;
-  d.b = b;
-  d.ok = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double e = fma(-b, y0, 1.0);
-  d.y = fma(y0, e, y0);
-#else
-  (void)y0;
-  d.y = 0.0;
-#endif
-  return d;
-}
+// divisor in [1, inf) unless NaN (a norm, shared_div_untested's first case): no test
+ORT_INLINE Div shared_div_ge1_seeded(double b, double y0) { return Div{b, rcp_seeded(b, y0)}; }
 
 // 1 / b for b = L^2 + M^2 + N^2 of a unit direction (a sphere's quadratic in the plain
 // form): y0 = 2 - b = (1 - (1 - b)^2) / b, so with |1 - b| <= 2^-27 (tested; false for
 // NaN) the seed's es is within 2^-54 + 2^-53 (2 - b rounds only for b < 1) and
-// shared_div_seeded's one step leaves es^2 < 2^-104. The test stands in for shared_div's
+// rcp_seeded's one step leaves es^2 < 2^-104. The test stands in for shared_div's
 // |b| <= 2^300 as well.
 template <class B>
-ORT_INLINE SharedDiv shared_div_unit(double b, B& bad) {
-  SharedDiv d;
-  d.b = b;
-  d.ok = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double y0 = 2.0 - b;
-  const double e = fma(-b, y0, 1.0);
-  d.y = fma(y0, e, y0);
+ORT_INLINE Div shared_div_unit(double b, B& bad) {
+  const Div d{b, rcp_seeded(b, 2.0 - b)};
   ORT_CHK(bad, !(::fabs(1.0 - b) <= 0x1p-27));
-#else
-  (void)bad;
-  d.y = 0.0;
-#endif
   return d;
 }
 
-ORT_INLINE double quot(double a, const SharedDiv& d) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double q0 = a * d.y;
-  const double r = fma(-d.b, q0, a);
-  return fma(r, d.y, q0);
-#else
-  return a / d.b;
-#endif
-}
-
-// The same quotient for a divisor known to be > 0 with the residual formed negated:
-// rn = fma(b, q0, -a) = -r exactly, and fma(-rn, y, q0) rounds q0 + r y exactly as
-// fma(r, y, q0) does, but an exact-zero numerator keeps its sign (+-0 / b = +-0): for
-// a = -0, rn = (-0) + (+0) = +0 and (-rn) y + q0 = (-0) + (-0) = -0, where the plain
-// form's r = +0 turns -0 / b into +0. The negations are free operand modifiers. (For
-// b < 0 the plain form is the one that is right for both zeros.)
-ORT_INLINE double quot_pos(double a, const SharedDiv& d) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const double q0 = a * d.y;
-  const double rn = fma(d.b, q0, -a);
-  return fma(-rn, d.y, q0);
-#else
-  return a / d.b;
-#endif
-}
+// ---- quotients: ort_core.h's quot / quot_pos (the latter for a divisor > 0: an exact-zero
+// numerator keeps its sign) ---------------------------------------------------------------
+ORT_INLINE double quot(double a, const Div& d) { return ort::quot(a, d.b, d.y); }
+ORT_INLINE double quot_pos(double a, const Div& d) { return ort::quot_pos(a, d.b, d.y); }
 
 // |a| >= 2^-300 (false for 0 and NaN); a numerator past 2^300 overflows into a
 // non-finite quotient (see the header)
@@ -334,13 +176,13 @@ ORT_INLINE bool num_ok(double a) { return ::fabs(a) >= 0x1p-300; }
 
 // a / b, |a| >= 2^-300
 template <class B>
-ORT_INLINE double sdiv(double a, const SharedDiv& d, B& bad) {
+ORT_INLINE double sdiv(double a, const Div& d, B& bad) {
   ORT_CHK(bad, !num_ok(a));
   return quot(a, d);
 }
 // a / b, |a| >= 2^-300 or a == +0 (coordinates on a symmetry plane)
 template <class B>
-ORT_INLINE double sdiv0(double a, const SharedDiv& d, B& bad) {
+ORT_INLINE double sdiv0(double a, const Div& d, B& bad) {
   ORT_CHK(bad, !(num_ok(a) || is_pos_zero(a)));
   return quot(a, d);
 }
@@ -348,7 +190,7 @@ ORT_INLINE double sdiv0(double a, const SharedDiv& d, B& bad) {
 // a / b as one IEEE division
 template <class B>
 ORT_INLINE double div(double a, double b, B& bad) {
-  const SharedDiv d = shared_div(b, bad);
+  const Div d = shared_div(b, bad);
   return sdiv0(a, d, bad);
 }
 
@@ -381,7 +223,7 @@ ORT_INLINE Ray generate_ray(const ort_segment& s, double px, double py,
   double hm;
   const double mag = sqrt_h(dx * dx + dy * dy + dz * dz, bad, hm);
   ORT_CHK(bad, (mag < 1e-9));  // the (0, 0, 1) branch of ray_generator.py:82-89
-  const SharedDiv dm = shared_div_seeded(mag, 2.0 * hm, bad);
+  const Div dm = shared_div_seeded(mag, 2.0 * hm, bad);
   // mag > 0: quot_pos is exact for zero numerators of either sign
   ORT_CHK(bad, !((num_ok(dx) || dx == 0.0) && (num_ok(dy) || dy == 0.0) &&
                  (num_ok(dz) || dz == 0.0)));
@@ -417,6 +259,8 @@ ORT_INLINE double distance_plane(const Ray& r, B& bad) { return div(-r.z, r.N, b
 // copy's one-root sphere branch (plain form only), which stays out of here: these kernels
 // sit at register and scratch edges, their a is not tested to be within 2^-27 of 1 (the
 // branch's error bounds lean on it), and nothing shares z + t N with the propagation.
+// (The two-root tail is written out in both: as one shared function it compiled to other
+// register assignments in six trace_kernel instantiations.)
 ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius_inf,
                                  bool& bad) {
   if (radius_inf) {
@@ -438,7 +282,7 @@ ORT_INLINE double distance_conic(const Ray& r, const ort_surface& s, bool radius
   }
   const double d = b * b - 4.0 * a * c;
   const double sd = sqrt(d, bad);
-  const SharedDiv a2 = shared_div(2.0 * a, bad);
+  const Div a2 = shared_div(2.0 * a, bad);
   // nonzero numerators (checked): quot_pos and quot agree for either sign of a
   const double n1 = -b + sd, n2 = -b - sd;
   ORT_CHK(bad, !(num_ok(n1) && num_ok(n2)));
@@ -556,7 +400,7 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
   ORT_CHK(bad, !(SS < 0x1p1020 && ::fabs(ac) < 0x1p1020));
   const double d = SS - ac;
   const double sd = sqrt(d, bad);
-  SharedDiv a1;
+  Div a1;
   if (PLAIN && sphere) {
     a1 = shared_div_unit(a, bad);
     // the predicted root: -S + sd (root 1) exactly when N R < 0; sd >= 0 or NaN
@@ -608,7 +452,7 @@ ORT_INLINE double distance_conic_folded(const Ray& r, const ort_surface& s, bool
 // |gam| <= u, so |g sqrt(X) - 1| < 6.9u + u + O(u^2) < 2^-50, whatever the hit height, where
 // v_rsq has e0 = 2^-20: the sequence's bounds hold with room (sqrt_seeded_h).
 //   q = 0 (vertex): w = 1, g = 1, dfdx = dfdy = +-0, X = 1: the seed is exact.
-//   w at its low end: 2^-53, the least positive fl(1 - q) (sqrt_1m_h); s <= 2^54 then, and
+//   w at its low end: 2^-53, the least positive fl(1 - q) (sqrt_untested_h); s <= 2^54 then, and
 //     no product above under- or overflows (|x|, |y| >= 2^-300 or +0, checked by sdiv0).
 //   w <= 0: g is NaN, and so are denom, the slopes, X and the normal: state_ok.
 // Nothing but the seed changes: mag is the same RN(sqrt(X)) and 2 hm seeds 1 / mag as
@@ -637,11 +481,11 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, bool 
   const double q = fma(fma(-s.r_sq, q0, a), s.inv_r2, q0);
   double h, g;
   if constexpr (PLAIN)
-    g = sqrt_1m_h(1.0 - q, h);
+    g = sqrt_untested_h(1.0 - q, h);
   else
     g = sqrt_h(1.0 - q, bad, h);
   const double denom = s.radius * g;
-  SharedDiv dd;
+  Div dd;
   bool seeded = false;  // the surface carries the bit
   if constexpr (PLAIN) {
     seeded = SPHERES || (s.flags & ORT_SURF_TWO_INV_R) != 0;
@@ -659,9 +503,9 @@ ORT_INLINE void normal_conic_rcp(double x, double y, const ort_surface& s, bool 
   if (PLAIN && seeded && sphere)
     mag = sqrt_seeded_h(X, g, hm);
   else
-    mag = sqrt_ge1_h(X, bad, hm);
+    mag = sqrt_untested_h(X, hm);
   // 1 / mag seeded by 2 h of mag's own root: |es| <= 1.5 e0^2 + 2^-51, es^2 after the step
-  const SharedDiv dm = shared_div_ge1_seeded(mag, 2.0 * hm);
+  const Div dm = shared_div_ge1_seeded(mag, 2.0 * hm);
   // dfdx = x / denom with x checked (|x| in [2^-300, 2^300] or +0) and |denom| <= 2^300:
   // |dfdx| >= 2^-600 or +-0, and |dfdx| <= mag -- in range for the positive divisor
   // mag, zeros of either sign included (quot_pos): no check left to make
@@ -701,29 +545,26 @@ ORT_INLINE double align_normal(const Ray& r, double& nx, double& ny, double& nz,
 // (the sign of a zero product is the xor of its factors' signs, which both sides share),
 // and a NaN on one side is a NaN on the other (never stored: state_ok). dot * dot is
 // |dot| |dot| likewise. So the raw normal, the signed dot and root_s = root with dot's sign
-// bit give the same three sums in the same order; root >= 0 or NaN (sqrt_1m), so putting
+// bit give the same three sums in the same order; root >= 0 or NaN (sqrt_untested), so putting
 // the bit on is the flip. dot == 0 and NaN take the exact path as before.
 template <bool PLAIN = false, class B>
 ORT_INLINE void refract(Ray& r, double nx, double ny, double nz, double u, double u_sq,
                         B& bad) {
+  double dot, root;  // PLAIN: the signed dot and root_s; else |dot| and the root
   if constexpr (PLAIN) {
-    const double dot = r.L * nx + r.M * ny + r.N * nz;
+    dot = r.L * nx + r.M * ny + r.N * nz;
     ORT_CHK(bad, !(::fabs(dot) > 0.0));
     const double v = u_sq * (1.0 - dot * dot);
-    const double root_s = with_sign_of(sqrt_1m(1.0 - v), dot);
-    const double L0 = r.L, M0 = r.M, N0 = r.N;
-    r.L = u * L0 + nx * root_s - u * nx * dot;
-    r.M = u * M0 + ny * root_s - u * ny * dot;
-    r.N = u * N0 + nz * root_s - u * nz * dot;
+    root = with_sign_of(sqrt_untested(1.0 - v), dot);
   } else {
-    const double dot = align_normal(r, nx, ny, nz, bad);
+    dot = align_normal(r, nx, ny, nz, bad);
     const double v = u_sq * (1.0 - dot * dot);
-    const double root = sqrt(1.0 - v, bad);
-    const double L0 = r.L, M0 = r.M, N0 = r.N;
-    r.L = u * L0 + nx * root - u * nx * dot;
-    r.M = u * M0 + ny * root - u * ny * dot;
-    r.N = u * N0 + nz * root - u * nz * dot;
+    root = sqrt(1.0 - v, bad);
   }
+  const double L0 = r.L, M0 = r.M, N0 = r.N;
+  r.L = u * L0 + nx * root - u * nx * dot;
+  r.M = u * M0 + ny * root - u * ny * dot;
+  r.N = u * N0 + nz * root - u * nz * dot;
 }
 
 // Refraction at a flat surface: the plane normal (0, 0, 1) (plane.py:79-98) or the
@@ -741,7 +582,7 @@ ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, B& bad) {
   const double v = u_sq * (1.0 - r.N * r.N);
   double root;
   if constexpr (PLAIN)
-    root = sqrt_1m(1.0 - v);
+    root = sqrt_untested(1.0 - v);
   else
     root = sqrt(1.0 - v, bad);
   const double uN = u * r.N;
@@ -754,7 +595,7 @@ ORT_INLINE void refract_flat(Ray& r, double u, double u_sq, B& bad) {
 // ---- Newton geometries (trace_kernel's deferred-check pass) --------------------------
 // The quotient for a divisor of either sign with a numerator that may be +-0: IEEE's
 // signed zero is quot_pos's for b > 0 and the plain form's for b < 0 (see quot_pos)
-ORT_INLINE double quot_signed(double a, const SharedDiv& d) {
+ORT_INLINE double quot_signed(double a, const Div& d) {
   return d.b > 0.0 ? quot_pos(a, d) : quot(a, d);
 }
 // numerator in range or an exact zero of either sign (quot_signed / quot_pos keep its sign)
@@ -768,11 +609,8 @@ ORT_INLINE bool num_ok0(double a) { return num_ok(a) || a == 0.0; }
 // b < 0) -- without quot_signed's two quotients and select. A zero divisor (q = 0)
 // gives an infinite reciprocal and non-finite quotients, as the signed form does.
 // |R| <= 2^149 (so |R| (1 + q) <= 2^150, R^2 <= 2^298: inside shared_div's range) is
-// tested once per evaluation (lens_range) instead of a test per divisor.
-ORT_INLINE SharedDiv shared_div_pos(double b) {
-  bool unused = false;
-  return shared_div_ge1(b, unused);  // (the same refinement, no test of its own)
-}
+// tested once per evaluation (lens_range) instead of a test per divisor
+// (shared_div_untested).
 ORT_INLINE bool lens_range(double R) { return ::fabs(R) <= 0x1p149; }
 
 // kSlope's direct slopes (ort_core.h): norm^2 < 1e28 checked (a steeper normal or NaN
@@ -788,11 +626,11 @@ ORT_INLINE void slope_out(double dfdx, double dfdy, double& nx, double& ny, doub
 }
 
 // the unit normal (dz/dx, dz/dy, -1) / norm from kSlope's direct slopes (norm^2 < 1e28
-// checked by slope_out): the tail of the kNormal evaluations, operation for operation
+// checked by slope_out), and the tail of sagnorm_even's and sagnorm_odd's kNormal mode
 ORT_INLINE void unit_normal_from_slope(double dfdx, double dfdy, double& nx, double& ny,
                                        double& nz, bool& bad) {
-  const double mag = sqrt_ge1(dfdx * dfdx + dfdy * dfdy + 1.0, bad);
-  const SharedDiv dm = shared_div_ge1(mag, bad);
+  const double mag = sqrt_untested(dfdx * dfdx + dfdy * dfdy + 1.0);  // >= 1
+  const Div dm = shared_div_untested(mag);                             // a norm
   ORT_CHK(bad, !(num_ok0(dfdx) && num_ok0(dfdy)));
   nx = quot_pos(dfdx, dm);
   ny = quot_pos(dfdy, dm);
@@ -810,15 +648,15 @@ ORT_INLINE double sagnorm_even(double x, double y, const ort_surface& s, PD C,
   ORT_CHK(bad, !lens_range(R));
   const double r2 = x * x + y * y;
   const double a = s.one_plus_k * r2;  // (1 + k) r2: +-0 at the vertex
-  const SharedDiv rr = shared_div_pos(s.r_sq);
+  const Div rr = shared_div_untested(s.r_sq);
   ORT_CHK(bad, !num_ok0(a));
   const double q = sqrt(1.0 - quot_pos(a, rr), bad);
-  const SharedDiv dz = shared_div_pos(aR * (1.0 + q));
+  const Div dz = shared_div_untested(aR * (1.0 + q));
   ORT_CHK(bad, !num_ok0(r2));
   double P, D;  // the term sums by Horner in r2 (ort_core.h even_horner)
   ort::even_horner(r2, C, nc, P, D);
   const double z = quot_pos(sR * r2, dz) + r2 * P;
-  const SharedDiv dd = shared_div_pos(aR * q);
+  const Div dd = shared_div_untested(aR * q);
   ORT_CHK(bad, !(num_ok0(x) && num_ok0(y)));
   double dfdx = quot_pos(sR * x, dd);
   double dfdy = quot_pos(sR * y, dd);
@@ -828,12 +666,7 @@ ORT_INLINE double sagnorm_even(double x, double y, const ort_surface& s, PD C,
     slope_out(dfdx, dfdy, nx, ny, nz, bad);
     return z;
   }
-  const double mag = sqrt_ge1(dfdx * dfdx + dfdy * dfdy + 1.0, bad);
-  const SharedDiv dm = shared_div_ge1(mag, bad);
-  ORT_CHK(bad, !(num_ok0(dfdx) && num_ok0(dfdy)));
-  nx = quot_pos(dfdx, dm);
-  ny = quot_pos(dfdy, dm);
-  nz = quot(-1.0, dm);
+  unit_normal_from_slope(dfdx, dfdy, nx, ny, nz, bad);
   return z;
 }
 
@@ -848,10 +681,10 @@ ORT_INLINE double sagnorm_odd(double x, double y, const ort_surface& s, PD C,
   const double r2 = x * x + y * y;
   const double r = sqrt(r2, bad);  // the vertex itself (r2 = 0) takes the exact path
   const double a = s.one_plus_k * r2;
-  const SharedDiv rr = shared_div_pos(s.r_sq);
+  const Div rr = shared_div_untested(s.r_sq);
   ORT_CHK(bad, !num_ok0(a));
   const double q = sqrt(1.0 - quot_pos(a, rr), bad);
-  const SharedDiv dz = shared_div_pos(aR * (1.0 + q));
+  const Div dz = shared_div_untested(aR * (1.0 + q));
   ORT_CHK(bad, !num_ok0(r2));
   double z = quot_pos(sR * r2, dz);
   double rp = r;
@@ -859,11 +692,11 @@ ORT_INLINE double sagnorm_odd(double x, double y, const ort_surface& s, PD C,
     z = z + C[i] * rp;
     rp = rp * r;
   }
-  const SharedDiv dd = shared_div_pos(aR * q);
+  const Div dd = shared_div_untested(aR * q);
   ORT_CHK(bad, !(num_ok0(x) && num_ok0(y)));
   double dfdx = quot_pos(sR * x, dd);
   double dfdy = quot_pos(sR * y, dd);
-  const SharedDiv dr = shared_div(r, bad);
+  const Div dr = shared_div(r, bad);
   double rq = quot_pos(1.0, dr);  // 1 / r
   for (int i = 0; i < nc; ++i) {
     const double f = (double)(i + 1);
@@ -879,12 +712,7 @@ ORT_INLINE double sagnorm_odd(double x, double y, const ort_surface& s, PD C,
     slope_out(dfdx, dfdy, nx, ny, nz, bad);
     return z;
   }
-  const double mag = sqrt_ge1(dfdx * dfdx + dfdy * dfdy + 1.0, bad);
-  const SharedDiv dm = shared_div_ge1(mag, bad);
-  ORT_CHK(bad, !(num_ok0(dfdx) && num_ok0(dfdy)));
-  nx = quot_pos(dfdx, dm);
-  ny = quot_pos(dfdy, dm);
-  nz = quot(-1.0, dm);
+  unit_normal_from_slope(dfdx, dfdy, nx, ny, nz, bad);
   return z;
 }
 
@@ -893,7 +721,7 @@ ORT_INLINE double newton_step_slope(const Ray& r, double t, double f, double fx,
                                     bool& bad) {
   const double df = fx * r.L + fy * r.M - r.N;
   const double dfs = ::fabs(df) > 1e-14 ? df : 1e-14;
-  const SharedDiv dd = shared_div(dfs, bad);
+  const Div dd = shared_div(dfs, bad);
   ORT_CHK(bad, !num_ok0(f));
   return t - quot_signed(f, dd);
 }
@@ -902,14 +730,14 @@ ORT_INLINE double newton_step_slope(const Ray& r, double t, double f, double fx,
 ORT_INLINE double newton_step(const Ray& r, double t, double f, double nx, double ny,
                               double nz, bool& bad) {
   const double nzs = ::fabs(nz) > 1e-14 ? nz : 1e-14;
-  const SharedDiv dn = shared_div(nzs, bad);
+  const Div dn = shared_div(nzs, bad);
   const double mnx = -nx, mny = -ny;
   ORT_CHK(bad, !(num_ok0(mnx) && num_ok0(mny)));
   const double fx = quot_signed(mnx, dn);
   const double fy = quot_signed(mny, dn);
   const double df = fx * r.L + fy * r.M - r.N;
   const double dfs = ::fabs(df) > 1e-14 ? df : 1e-14;
-  const SharedDiv dd = shared_div(dfs, bad);
+  const Div dd = shared_div(dfs, bad);
   ORT_CHK(bad, !num_ok0(f));
   return t - quot_signed(f, dd);
 }

@@ -16,63 +16,19 @@ import itertools
 import numpy as np
 import pytest
 
+from tests._closed import CONIC, MIRROR, TRIPLET, optic, same_as_oracle, same_bits
+from tests._closed import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
 N_RAYS = 100  # 64 + 36
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-
-    if not t.cuda.is_available():
-        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
-    from optiland_pr_amd import _native
-
-    _native.load()
-    return t
-
-
 def _optic(rows, scale=1.0):
-    """A centred lens from add_surface rows; radii and thicknesses times scale."""
-    from optiland_pr_amd.optic import Optic
+    """A centred lens from add_surface rows; radii and thicknesses times scale, the
+    entrance pupil diameter 10 at every scale."""
+    return optic(rows, scale, scale_epd=False)
 
-    lens = Optic()
-    for i, row in enumerate(rows):
-        kw = dict(row)
-        for key in ("radius", "thickness"):
-            if key in kw and np.isfinite(kw[key]):
-                kw[key] = kw[key] * scale
-        lens.add_surface(index=i, **kw)
-    lens.set_aperture(aperture_type="EPD", value=10)
-    lens.set_field_type(field_type="angle")
-    lens.add_field(y=0)
-    lens.add_wavelength(value=0.55, is_primary=True)
-    return lens
-
-
-_TRIPLET = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=22.01359, thickness=3.25896, material="SK16"),
-    dict(radius=-435.76044, thickness=6.00755),
-    dict(radius=-22.21328, thickness=0.99997, material=("F2", "schott")),
-    dict(radius=20.29192, thickness=4.75041, is_stop=True),
-    dict(radius=79.68360, thickness=2.95208, material="SK16"),
-    dict(radius=-18.39533, thickness=42.20778),
-    dict(),
-]
-_CONIC = [dict(r) for r in _TRIPLET]
-_CONIC[1]["conic"] = -0.6
-_CONIC[4]["conic"] = 0.8
-_CONIC[6]["conic"] = 1.2
-_MIRROR = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=40.0, thickness=5.0, material="SK16"),
-    dict(radius=np.inf, thickness=30.0),
-    dict(radius=-120.0, thickness=-25.0, material="mirror"),
-    dict(),
-]
 
 # name -> (lens factory, wavelength, first traced surface, scale of every length).
 # The lowered table starts at the first surface behind the object: 0 is the front sphere;
@@ -82,12 +38,12 @@ CASES = {
     "dg_plane_first": (lambda: _sample("DoubleGauss"), 0.5876, 3, 1.0),
     "cooke_sphere_first": (lambda: _sample("CookeTriplet"), 0.55, 0, 1.0),
     "cooke_plane_first": (lambda: _sample("CookeTriplet"), 0.55, 6, 1.0),
-    "conic": (lambda: _optic(_CONIC), 0.55, 0, 1.0),
-    "conic_from_second": (lambda: _optic(_CONIC), 0.55, 1, 1.0),
-    "mirror": (lambda: _optic(_MIRROR), 0.55, 0, 1.0),
-    "mirror_plane_first": (lambda: _optic(_MIRROR), 0.55, 1, 1.0),
-    "scaled_up": (lambda: _optic(_TRIPLET, 2.0**140), 0.55, 0, 2.0**140),
-    "scaled_down": (lambda: _optic(_TRIPLET, 2.0**-140), 0.55, 0, 2.0**-140),
+    "conic": (lambda: _optic(CONIC), 0.55, 0, 1.0),
+    "conic_from_second": (lambda: _optic(CONIC), 0.55, 1, 1.0),
+    "mirror": (lambda: _optic(MIRROR), 0.55, 0, 1.0),
+    "mirror_plane_first": (lambda: _optic(MIRROR), 0.55, 1, 1.0),
+    "scaled_up": (lambda: _optic(TRIPLET, 2.0**140), 0.55, 0, 2.0**140),
+    "scaled_down": (lambda: _optic(TRIPLET, 2.0**-140), 0.55, 0, 2.0**-140),
 }
 
 
@@ -110,26 +66,6 @@ def _rays(scale):
     return cols
 
 
-def _same_bits(got, exp, what):
-    for a in FIELDS:
-        g, e = np.asarray(got[a]), np.asarray(exp[a])
-        np.testing.assert_array_equal(g.view(np.uint64), e.view(np.uint64), err_msg=f"{what} {a}")
-
-
-def _same_as_oracle(got, ref, what):
-    for a in FIELDS:
-        g, r = np.asarray(got[a]), np.asarray(getattr(ref, a))
-        np.testing.assert_array_equal(np.isnan(g), np.isnan(r), err_msg=f"{what} {a} NaN")
-        ok = ~np.isnan(r)
-        if a == "i":
-            with np.errstate(all="ignore"):
-                np.testing.assert_allclose(g[ok], r[ok], rtol=1e-12, atol=0)
-            continue
-        np.testing.assert_array_equal(g[ok], r[ok], err_msg=f"{what} {a}")
-        np.testing.assert_array_equal(np.signbit(g[ok]), np.signbit(r[ok]),
-                                      err_msg=f"{what} sign of {a}")
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_caller_rays_fast_equals_exact_and_oracle(torch, case):
     """The caller-supplied-ray path (no F_GEN): rays entering with x, y = +0 / -0, on the
@@ -148,12 +84,12 @@ def test_caller_rays_fast_equals_exact_and_oracle(torch, case):
         trace_rays(dl, rin, rout, start_surface=start, exact_only=exact)
         torch.cuda.synchronize()
         outs[exact] = rout.numpy()
-    _same_bits(outs[False], outs[True], case)
+    same_bits(outs[False], outs[True], case)
     with np.errstate(all="ignore"):
         ref = trace_np.trace_segment(
             dl.table, trace_np.Rays(x.copy(), y.copy(), z.copy(), L.copy(), M.copy(), N.copy(),
                                     np.ones(N_RAYS)), 0, start=start).rays
-    _same_as_oracle(outs[False], ref, case)
+    same_as_oracle(outs[False], ref, case)
     assert np.isfinite(outs[False]["x"]).sum() > N_RAYS // 2  # the case traces real rays
 
 
@@ -182,7 +118,7 @@ def test_generated_rays_fast_equals_exact_and_oracle(torch, lens_name):
             torch.cuda.synchronize()
             outs[exact] = out.numpy()
         what = f"{lens_name} ({hx},{hy})"
-        _same_bits(outs[False], outs[True], what)
+        same_bits(outs[False], outs[True], what)
         with np.errstate(all="ignore"):
             ref = trace_np.trace_segment(dl.table, trace_np.generate_rays(seg[0], px, py), 0).rays
-        _same_as_oracle(outs[False], ref, what)
+        same_as_oracle(outs[False], ref, what)

@@ -4,8 +4,8 @@ single sign flip (dot's sign bit onto the root instead of three flipped normal c
 
 Every comparison: a default launch and an ORT_OPT_EXACT launch -- every lane through the
 generic exact re-trace, which has neither -- store identical bytes in all eight outputs,
-NaN payloads and signed zeros included (test_gpu_closed_spheres.py's _check, which also
-sets the oracle beside them). Ray counts 1, 63, 64, 65, 256, 257: lane, wave and block
+NaN payloads and signed zeros included (tests/_closed.py's check_segments, which also sets
+the oracle beside them). Ray counts 1, 63, 64, 65, 256, 257: lane, wave and block
 edges; one wavelength row per wave (F_MONO) and rows that change inside a wave.
 
 Lanes the guard flags (hits above half the z-extent of their chord: the near-hemispherical
@@ -15,10 +15,9 @@ not visible here (tests/test_one_root_cpu.py counts the flags of the model).
 import numpy as np
 import pytest
 
+from tests._closed import HALF_BALL, check_segments, launch_segments, optic, same_bits, selected
+from tests._closed import torch  # noqa: F401
 from tests._plain_lenses import build
-from tests.test_gpu_closed_plain import _same_bits
-from tests.test_gpu_closed_spheres import _check, _launch, _segments, _selected, torch  # noqa: F401
-from tests.test_gpu_closed_unit_seeds import _optic
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +45,7 @@ _ONE_CONIC = [  # plain, not all spheres: the uniform sphere branch beside today
     dict(radius=-80.0, thickness=40.0),
     dict(),
 ]
-_HEMISPHERE = [  # front radius 5 under an entrance pupil of 9.5: r / |R| up to 0.95
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=5.0, thickness=6.0, material="SK16", is_stop=True),
-    dict(radius=-40.0, thickness=20.0),
-    dict(),
-]
+_HEMISPHERE = HALF_BALL  # front radius 5 under an entrance pupil of 9.5: r / |R| up to 0.95
 ROWS = {"doublet": (_DOUBLET, 10.0, True), "mirrored": (_MIRRORED, 10.0, True),
         "one_conic": (_ONE_CONIC, 10.0, False), "hemisphere": (_HEMISPHERE, 9.5, True)}
 
@@ -63,7 +57,7 @@ def lenses(torch):  # noqa: F811
 
     out = {}
     for name, (rows, epd, _) in ROWS.items():
-        lens = _optic(rows, epd=epd, fields=(0.0, 10.0))
+        lens = optic(rows, epd=epd, fields=(0.0, 10.0))
         out[name] = {True: (lens, lens_for(lens, [WLS[0]])), False: (lens, lens_for(lens, list(WLS)))}
     return out
 
@@ -75,10 +69,10 @@ def test_default_against_exact_and_oracle(torch, lenses, name, mono):  # noqa: F
 
     lens, dl = lenses[name][mono]
     assert dl.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN
-    assert _selected(dl) == ROWS[name][2]
+    assert selected(dl) == ROWS[name][2]
     finite = 0.0
     for n in COUNTS:
-        fast = _check(torch, dl, lens, n, mono, f"{name} n={n} mono={mono}")
+        fast = check_segments(torch, dl, lens, n, mono, f"{name} n={n} mono={mono}")
         finite = max(finite, np.isfinite(fast["x"]).mean())
     assert finite > 0.5  # the lens passes rays: the fast pass is what ran
 
@@ -95,8 +89,8 @@ def test_hemisphere_is_filled(torch, lenses):  # noqa: F811
     h = np.concatenate([np.linspace(0.0, 1.0, 120), np.linspace(1.0, 1.2, 9)[1:]])
     th = np.arange(h.size) * 2.399963
     px, py = h * np.cos(th), h * np.sin(th)
-    fast = _launch(torch, dl, [seg], px.size, px, py, False)
-    _same_bits(fast, _launch(torch, dl, [seg], px.size, px, py, True), "hemisphere fill")
+    fast = launch_segments(torch, dl, [seg], px.size, px, py, False)
+    same_bits(fast, launch_segments(torch, dl, [seg], px.size, px, py, True), "hemisphere fill")
     r_over_R = h * 9.5 / 2 / 5.0
     assert np.isnan(fast["x"][r_over_R > 1.0 + 1e-9]).all()  # past the rim: misses
     assert np.isfinite(fast["x"][r_over_R < 0.5]).all()
@@ -116,8 +110,8 @@ def test_axis_and_meridional_points(torch, lenses):  # noqa: F811
         lens, dl = lenses[name][True]
         for hy in (0.0, 1.0):
             seg = segment_params(lens, 0.0, hy, 0)
-            fast = _launch(torch, dl, [seg], px.size, px, py, False)
-            _same_bits(fast, _launch(torch, dl, [seg], px.size, px, py, True), f"{name} hy={hy}")
+            fast = launch_segments(torch, dl, [seg], px.size, px, py, False)
+            same_bits(fast, launch_segments(torch, dl, [seg], px.size, px, py, True), f"{name} hy={hy}")
             assert np.isfinite(fast["x"]).all()
             if hy == 0.0:  # the axial ray stays on the axis, zeros and all
                 assert np.all(fast["x"][:4] == 0.0) and np.all(fast["y"][:4] == 0.0)
@@ -130,5 +124,5 @@ def test_sample_objectives(torch, name, mono):  # noqa: F811
 
     lens, wl = build(name)
     dl = lens_for(lens, [wl] if mono else [wl, wl + 0.05])
-    fast = _check(torch, dl, lens, 257, mono, f"{name} mono={mono}")
+    fast = check_segments(torch, dl, lens, 257, mono, f"{name} mono={mono}")
     assert np.isfinite(fast["x"]).all()

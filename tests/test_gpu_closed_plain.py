@@ -14,52 +14,11 @@ the cases on them pin.
 import numpy as np
 import pytest
 
+from tests._closed import FIELDS, Ref, pupil, same_as_oracle, same_bits
+from tests._closed import torch  # noqa: F401
 from tests._plain_lenses import NOT_PLAIN, PLAIN, build
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-
-    if not t.cuda.is_available():
-        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
-    from optiland_pr_amd import _native
-
-    _native.load()
-    return t
-
-
-def _same_bits(got, exp, what):
-    for a in FIELDS:
-        g, e = np.asarray(got[a]), np.asarray(exp[a])
-        np.testing.assert_array_equal(g.view(np.uint64), e.view(np.uint64), err_msg=f"{what} {a}")
-
-
-def _same_as_oracle(got, ref, what):
-    for a in FIELDS:
-        g, r = np.asarray(got[a]), np.asarray(getattr(ref, a))
-        np.testing.assert_array_equal(np.isnan(g), np.isnan(r), err_msg=f"{what} {a} NaN")
-        ok = ~np.isnan(r)
-        if a == "i":
-            with np.errstate(all="ignore"):
-                np.testing.assert_allclose(g[ok], r[ok], rtol=1e-12, atol=0)
-            continue
-        np.testing.assert_array_equal(g[ok], r[ok], err_msg=f"{what} {a}")
-        np.testing.assert_array_equal(np.signbit(g[ok]), np.signbit(r[ok]),
-                                      err_msg=f"{what} sign of {a}")
-
-
-def _pupil(n, seed=5):
-    """n points of the unit disc; the first is the centre, (+0, -0)."""
-    rng = np.random.default_rng(seed)
-    r, th = np.sqrt(rng.uniform(0, 1, n)), rng.uniform(0, 2 * np.pi, n)
-    px, py = r * np.cos(th), r * np.sin(th)
-    px[0], py[0] = 0.0, -0.0
-    return px, py
 
 
 def _trace_generated(torch, dl, segs, px, py, seg_len, exact):
@@ -81,12 +40,7 @@ def _oracle_generated(dl, segs, px, py):
         for sg in segs:
             parts.append(trace_np.trace_segment(
                 dl.table, trace_np.generate_rays(sg, px, py), int(sg["lambda_idx"])).rays)
-    return {a: np.concatenate([getattr(p, a) for p in parts]) for a in FIELDS}
-
-
-class _Ref:
-    def __init__(self, d):
-        self.__dict__.update(d)
+    return Ref({a: np.concatenate([getattr(p, a) for p in parts]) for a in FIELDS})
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
@@ -101,11 +55,11 @@ def test_plain_lenses_generated_rays(torch, name, n):
     lens, wl = build(name)
     dl = lens_for(lens, [wl])
     assert dl.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN
-    px, py = _pupil(n)
+    px, py = pupil(n)
     segs = [segment_params(lens, 0.0, 0.7, 0)]
     fast = _trace_generated(torch, dl, segs, px, py, n, False)
-    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), f"{name} n={n}")
-    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), f"{name} n={n}")
+    same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), f"{name} n={n}")
+    same_as_oracle(fast, _oracle_generated(dl, segs, px, py), f"{name} n={n}")
     assert np.isfinite(fast["x"]).all()
 
 
@@ -135,12 +89,12 @@ def test_every_first_surface(torch, name):
             torch.cuda.synchronize()
             outs[exact] = rout.numpy()
         what = f"{name} start={start}"
-        _same_bits(outs[False], outs[True], what)
+        same_bits(outs[False], outs[True], what)
         with np.errstate(all="ignore"):
             ref = trace_np.trace_segment(
                 dl.table, trace_np.Rays(*(c.copy() for c in cols), np.ones(n)), 0,
                 start=start).rays
-        _same_as_oracle(outs[False], ref, what)
+        same_as_oracle(outs[False], ref, what)
 
 
 @pytest.mark.parametrize("name", sorted(PLAIN))
@@ -153,7 +107,7 @@ def test_every_first_surface_generated(torch, name):
     lens, wl = build(name)
     dl = lens_for(lens, [wl])
     n = 65
-    px, py = _pupil(n)
+    px, py = pupil(n)
     seg = np.stack([segment_params(lens, 0.0, 0.0, 0)])
     pxd, pyd = torch.as_tensor(px, device="cuda"), torch.as_tensor(py, device="cuda")
     for start in range(dl.table.n_surfaces):
@@ -163,7 +117,7 @@ def test_every_first_surface_generated(torch, name):
             trace_pupil(dl, seg, pxd, pyd, out, n, n, n, start_surface=start, exact_only=exact)
             torch.cuda.synchronize()
             outs[exact] = out.numpy()
-        _same_bits(outs[False], outs[True], f"{name} generated start={start}")
+        same_bits(outs[False], outs[True], f"{name} generated start={start}")
 
 
 def test_three_wavelengths(torch):
@@ -175,12 +129,12 @@ def test_three_wavelengths(torch):
     lens, _ = build("DoubleGauss")
     wls = [0.4861, 0.5876, 0.6563]
     dl = lens_for(lens, wls)
-    px, py = _pupil(64)
+    px, py = pupil(64)
     segs = [segment_params(lens, 0.0, hy, lam) for lam in (0, 1, 2) for hy in (0.0, 1.0)]
     assert [int(s["lambda_idx"]) for s in segs] == [0, 0, 1, 1, 2, 2]
     fast = _trace_generated(torch, dl, segs, px, py, 64, False)
-    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, 64, True), "three wavelengths")
-    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), "three wavelengths")
+    same_bits(fast, _trace_generated(torch, dl, segs, px, py, 64, True), "three wavelengths")
+    same_as_oracle(fast, _oracle_generated(dl, segs, px, py), "three wavelengths")
     # the rows differ: the last wavelength's rays are not the first's
     assert not np.array_equal(fast["y"][:64], fast["y"][256:320])
 
@@ -202,11 +156,11 @@ def test_lenses_that_are_not_plain(torch, case):
     else:
         assert not dl.c.frame_flags & _abi.LENS_PLAIN
     n = 257
-    px, py = _pupil(n)
+    px, py = pupil(n)
     segs = [segment_params(lens, 0.0, 0.0, 0)]
     fast = _trace_generated(torch, dl, segs, px, py, n, False)
-    _same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), case)
-    _same_as_oracle(fast, _Ref(_oracle_generated(dl, segs, px, py)), case)
+    same_bits(fast, _trace_generated(torch, dl, segs, px, py, n, True), case)
+    same_as_oracle(fast, _oracle_generated(dl, segs, px, py), case)
 
 
 @pytest.mark.parametrize("name", sorted(PLAIN))
@@ -220,7 +174,7 @@ def test_bit_leaves_results_alone(torch, name):
     lens, wl = build(name)
     dl = lens_for(lens, [wl])
     n = 4099
-    px, py = _pupil(n)
+    px, py = pupil(n)
     segs = [segment_params(lens, 0.0, 1.0, 0)]
     on = _trace_generated(torch, dl, segs, px, py, n, False)
     flags = dl.c.frame_flags
@@ -230,4 +184,4 @@ def test_bit_leaves_results_alone(torch, name):
         off = _trace_generated(torch, dl, segs, px, py, n, False)
     finally:
         dl.c.frame_flags = flags
-    _same_bits(on, off, f"{name} plain bit on / off")
+    same_bits(on, off, f"{name} plain bit on / off")

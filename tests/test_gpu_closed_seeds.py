@@ -1,5 +1,5 @@
 """The closed-form kernel's fast pass with its reciprocals seeded from the square roots
-beside them (ort_fastpath.h: sqrt_ge1_h + shared_div_ge1_seeded for the conic normal's
+beside them (ort_fastpath.h: sqrt_untested_h + shared_div_ge1_seeded for the conic normal's
 magnitude, sqrt_h + shared_div_seeded for the generated ray's norm), against
 ORT_OPT_EXACT -- the same kernel with every lane sent through its exact re-trace, whose
 divisions are ort_core.h's own v_rcp-based sequences -- and against the NumPy oracle.
@@ -16,64 +16,17 @@ the default launch's kernel time beside the exact launch's instead.
 import numpy as np
 import pytest
 
+from tests._closed import (CONIC, MIRROR, N_ORACLE, TRIPLET, optic, pupils_fixture, same_as_oracle,
+                           same_bits)
+from tests._closed import torch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
-N_ORACLE = 4099
-N_PUPIL = 1 << 18
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-
-    if not t.cuda.is_available():
-        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
-    from optiland_pr_amd import _native
-
-    _native.load()
-    return t
-
-
-def _same_bits(got, exp, what):
-    for a in FIELDS:
-        g, e = np.asarray(got[a]), np.asarray(exp[a])
-        np.testing.assert_array_equal(g.view(np.uint64), e.view(np.uint64), err_msg=f"{what} {a}")
-
-
-def _same_as_oracle(got, ref, what, sel=slice(None)):
-    for a in FIELDS:
-        g, r = np.asarray(got[a])[sel], np.asarray(getattr(ref, a))
-        np.testing.assert_array_equal(np.isnan(g), np.isnan(r), err_msg=f"{what} {a} NaN")
-        ok = ~np.isnan(r)
-        if a == "i":
-            with np.errstate(all="ignore"):
-                np.testing.assert_allclose(g[ok], r[ok], rtol=1e-12, atol=0)
-            continue
-        np.testing.assert_array_equal(g[ok], r[ok], err_msg=f"{what} {a}")
-        np.testing.assert_array_equal(np.signbit(g[ok]), np.signbit(r[ok]),
-                                      err_msg=f"{what} sign of {a}")
-
 
 # ---- generated rays (F_GEN, the benchmark's kernel) ------------------------------------
 
-@pytest.fixture(scope="module")
-def pupils():
-    """name -> (px, py): three seeds of 2^18 random pupil points, the uniform 128 grid, and
-    the uniform 129 grid, whose centre column and row are +0."""
-    from optiland_pr_amd.distribution import RandomDistribution, UniformDistribution
-
-    out = {}
-    for seed in (1, 2, 3):
-        d = RandomDistribution(seed=seed)
-        d.generate_points(N_PUPIL)
-        out[f"seed{seed}"] = (d.x.copy(), d.y.copy())
-    for n in (128, 129):
-        d = UniformDistribution()
-        d.generate_points(n)
-        out[f"uniform{n}"] = (np.ascontiguousarray(d.x), np.ascontiguousarray(d.y))
-    assert np.any((out["uniform129"][0] == 0.0) & ~np.signbit(out["uniform129"][0]))
-    return out
+# three seeds of 2^18 random pupil points, the uniform 128 grid, and the uniform 129 grid,
+# whose centre column and row are +0
+pupils = pupils_fixture(1 << 18, seeds=(1, 2, 3), grids=(128, 129))
 
 
 @pytest.mark.parametrize("hy", [0.0, 0.7, 1.0])
@@ -98,56 +51,23 @@ def test_generated_rays_fast_equals_exact_and_oracle(torch, pupils, lens_name, h
             torch.cuda.synchronize()
             outs[exact] = out.numpy()
         what = f"{lens_name} hy={hy} {name}"
-        _same_bits(outs[False], outs[True], what)
+        same_bits(outs[False], outs[True], what)
         sel = np.arange(N_ORACLE) * (n // N_ORACLE)
         with np.errstate(all="ignore"):
             ref = trace_np.trace_segment(
                 dl.table, trace_np.generate_rays(seg[0], px[sel], py[sel]), 0).rays
-        _same_as_oracle(outs[False], ref, what, sel)
+        same_as_oracle(outs[False], ref, what, sel)
         assert np.isfinite(outs[False]["x"]).mean() > 0.5  # the case traces real rays
 
 
 # ---- caller rays (ort_trace_sequential) ------------------------------------------------
 
 def _optic(rows, scale=1.0):
-    """A centred lens from add_surface rows; radii and thicknesses times scale."""
-    from optiland_pr_amd.optic import Optic
-
-    lens = Optic()
-    for i, row in enumerate(rows):
-        kw = dict(row)
-        for key in ("radius", "thickness"):
-            if key in kw and np.isfinite(kw[key]):
-                kw[key] = kw[key] * scale
-        lens.add_surface(index=i, **kw)
-    lens.set_aperture(aperture_type="EPD", value=10)
-    lens.set_field_type(field_type="angle")
-    lens.add_field(y=0)
-    lens.add_wavelength(value=0.55, is_primary=True)
-    return lens
+    """A centred lens from add_surface rows; radii and thicknesses times scale, the
+    entrance pupil diameter 10 at every scale (caller rays: no pupil)."""
+    return optic(rows, scale, scale_epd=False)
 
 
-_TRIPLET = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=22.01359, thickness=3.25896, material="SK16"),
-    dict(radius=-435.76044, thickness=6.00755),
-    dict(radius=-22.21328, thickness=0.99997, material=("F2", "schott")),
-    dict(radius=20.29192, thickness=4.75041, is_stop=True),
-    dict(radius=79.68360, thickness=2.95208, material="SK16"),
-    dict(radius=-18.39533, thickness=42.20778),
-    dict(),
-]
-_CONIC = [dict(r) for r in _TRIPLET]
-_CONIC[1]["conic"] = -0.6
-_CONIC[4]["conic"] = 0.8
-_CONIC[6]["conic"] = 1.2
-_MIRROR = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=40.0, thickness=5.0, material="SK16"),
-    dict(radius=np.inf, thickness=30.0),
-    dict(radius=-120.0, thickness=-25.0, material="mirror"),
-    dict(),
-]
 # unit radii: scaled by s, the front radius is s itself
 _SINGLET = [
     dict(radius=np.inf, thickness=np.inf),
@@ -183,21 +103,21 @@ def _check_caller_rays(torch, lens, cols, what, wl=0.55, min_finite=0.5):
         trace_rays(dl, rin, rout, exact_only=exact)
         torch.cuda.synchronize()
         outs[exact] = rout.numpy()
-    _same_bits(outs[False], outs[True], what)
+    same_bits(outs[False], outs[True], what)
     with np.errstate(all="ignore"):
         ref = trace_np.trace_segment(
             dl.table, trace_np.Rays(x.copy(), y.copy(), z.copy(), L.copy(), M.copy(), N.copy(),
                                     np.ones(n)), 0).rays
-    _same_as_oracle(outs[False], ref, what)
+    same_as_oracle(outs[False], ref, what)
     assert np.isfinite(outs[False]["x"]).mean() >= min_finite, what
     return outs[False]
 
 
 LENSES = {
-    "conic": (_CONIC, 1.0),
-    "mirror": (_MIRROR, 1.0),
-    "scaled_up": (_TRIPLET, 2.0**140),
-    "scaled_down": (_TRIPLET, 2.0**-140),
+    "conic": (CONIC, 1.0),
+    "mirror": (MIRROR, 1.0),
+    "scaled_up": (TRIPLET, 2.0**140),
+    "scaled_down": (TRIPLET, 2.0**-140),
 }
 
 
@@ -216,7 +136,7 @@ def test_scaled_directions(torch, factor):
     seeded magnitude meets normals of rays the reference traces unnormalised. All stay on
     the fast pass here; which pass a lane took cannot be observed, only its bits."""
     x, y, z, L, M, N = _random_rays(N_ORACLE, 20.0, 12)
-    _check_caller_rays(torch, _optic(_TRIPLET), (x, y, z, L * factor, M * factor, N * factor),
+    _check_caller_rays(torch, _optic(TRIPLET), (x, y, z, L * factor, M * factor, N * factor),
                        f"directions x {factor!r}")
 
 
@@ -251,6 +171,6 @@ def test_vertex_and_rim_hits(torch):
             for cx, cy in ((1.0, 0.0), (0.0, -1.0), (0.6, 0.8)):
                 rows.append((h * cx, h * cy, -10.0, 0.0, 0.0, 1.0))
     cols = [np.array(c, dtype=np.float64) for c in zip(*rows)]
-    got = _check_caller_rays(torch, _optic(_TRIPLET), cols, "vertex and rim", min_finite=0.0)
+    got = _check_caller_rays(torch, _optic(TRIPLET), cols, "vertex and rim", min_finite=0.0)
     # vertex rays trace through (not all: the oracle, too, gives NaN for some zero patterns)
     assert np.isfinite(got["x"][:11]).any()

@@ -18,28 +18,17 @@ import dataclasses
 import numpy as np
 import pytest
 
-import tests.test_gpu_closed_sphere_seeds as seeds
+from tests._closed import (check_generated, check_segments, launch_segments, pupil, pupils_fixture,
+                           same_bits, scaled_singlets_case, segments, selected,
+                           vertex_and_rim_case)
+from tests._closed import torch  # noqa: F401
 from tests._plain_lenses import build
-from tests.test_gpu_closed_plain import _Ref, _pupil, _same_as_oracle, _same_bits
-from tests.test_gpu_closed_unit_seeds import _check_generated, pupils  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
 LENSES = {"DoubleGauss": (0.5876, 0.4861), "CookeTriplet": (0.55, 0.65)}
 COUNTS = (1, 63, 64, 65, 255, 256, 257, 300)  # lane, wave and block (256) edges
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-
-    if not t.cuda.is_available():
-        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
-    from optiland_pr_amd import _native
-
-    _native.load()
-    return t
+pupils = pupils_fixture(1 << 16, seeds=(4,), grids=(129,))  # test_gpu_closed_unit_seeds.py's
 
 
 @pytest.fixture(scope="module")
@@ -54,72 +43,13 @@ def lenses(torch):
     return out
 
 
-def _selected(dl):
-    from optiland_pr_amd import _abi
-
-    return (dl.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN
-            and dl.c.form_flags == _abi.LENS_SPHERES)
-
-
-def _segments(lens, n, mono):
-    """-> (segments, seg_len). mono: one segment of n rays. Otherwise two segments on two
-    wavelength rows whose boundary lies inside a wave (seg_len no multiple of 64), so the
-    launch is not F_MONO; the second may be short or, for n = 1, empty."""
-    from optiland_pr_amd.lowering import segment_params
-
-    if mono:
-        return [segment_params(lens, 0.0, 0.7, 0)], n
-    s = (n + 1) // 2
-    if s % 64 == 0:
-        s += 1
-    return [segment_params(lens, 0.0, 0.7, 0), segment_params(lens, 0.0, 1.0, 1)], s
-
-
-def _launch(torch, dl, segs, seg_len, px, py, exact, start=0):
-    from optiland_pr_amd.raytrace import RealRays, trace_pupil
-
-    n = px.size
-    out = RealRays.empty(n, 0.55)
-    trace_pupil(dl, np.stack(segs), torch.as_tensor(px, device="cuda"),
-                torch.as_tensor(py, device="cuda"), out, n, seg_len, n, pupil_per_ray=True,
-                start_surface=start, exact_only=exact)
-    torch.cuda.synchronize()
-    return out.numpy()
-
-
-def _oracle(table, segs, seg_len, px, py):
-    from oracle import trace_np
-
-    parts = []
-    with np.errstate(all="ignore"):
-        for k, sg in enumerate(segs):
-            sl = slice(k * seg_len, (k + 1) * seg_len)
-            if px[sl].size == 0:
-                continue
-            parts.append(trace_np.trace_segment(
-                table, trace_np.generate_rays(sg, px[sl], py[sl]), int(sg["lambda_idx"])).rays)
-    return _Ref({a: np.concatenate([getattr(p, a) for p in parts]) for a in FIELDS})
-
-
-def _check(torch, dl, lens, n, mono, what, start=0, oracle=True):
-    px, py = _pupil(n)
-    segs, seg_len = _segments(lens, n, mono)
-    if not mono:
-        assert dl.c.n_lambda == 2 and len(segs) == 2 and seg_len % 64 != 0
-    fast = _launch(torch, dl, segs, seg_len, px, py, False, start)
-    _same_bits(fast, _launch(torch, dl, segs, seg_len, px, py, True, start), what)
-    if oracle:
-        _same_as_oracle(fast, _oracle(dl.table, segs, seg_len, px, py), what)
-    return fast
-
-
 @pytest.mark.parametrize("mono", [True, False], ids=["mono", "rows"])
 @pytest.mark.parametrize("n", COUNTS)
 @pytest.mark.parametrize("name", sorted(LENSES))
 def test_default_against_exact_and_oracle(torch, lenses, name, n, mono):
     lens, dl = lenses[name][mono]
-    assert _selected(dl)
-    fast = _check(torch, dl, lens, n, mono, f"{name} n={n} mono={mono}")
+    assert selected(dl)
+    fast = check_segments(torch, dl, lens, n, mono, f"{name} n={n} mono={mono}")
     assert np.isfinite(fast["x"]).all()
 
 
@@ -144,11 +74,12 @@ def test_surface_starts_and_counts(torch, lenses, name, mono):
     total = dl.table.n_surfaces
     for count in (total, total - 1, 2, 1):
         cut = dl if count == total else _cut(dl, count)
-        assert _selected(cut) and cut.table.n_surfaces == count
+        assert selected(cut) and cut.table.n_surfaces == count
         for start in range(count):
             for n in (65, 300):
-                _check(torch, cut, lens, n, mono, f"{name} {count} surfaces start={start} n={n}",
-                       start=start, oracle=start == 0)
+                check_segments(torch, cut, lens, n, mono,
+                               f"{name} {count} surfaces start={start} n={n}", start=start,
+                               oracle=start == 0)
 
 
 def _conic_lens(dl):
@@ -212,14 +143,14 @@ def test_lenses_that_are_not_all_spheres(torch, lenses, case, mono):
     lens, dl = lenses["DoubleGauss"][mono]
     off = DeviceLens(dataclasses.replace(dl.table, surfaces=NOT_SPHERES[case](dl)))
     assert off.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN
-    assert off.c.form_flags == 0 and not _selected(off)
+    assert off.c.form_flags == 0 and not selected(off)
     for n in (65, 300):
-        _check(torch, off, lens, n, mono, f"{case} n={n}")
+        check_segments(torch, off, lens, n, mono, f"{case} n={n}")
     if case == "unseeded":  # the record's bit changes no result: the same bits as the lens
-        px, py = _pupil(300)
-        segs, seg_len = _segments(lens, 300, mono)
-        _same_bits(_launch(torch, off, segs, seg_len, px, py, False),
-                   _launch(torch, dl, segs, seg_len, px, py, False), "unseeded against seeded")
+        px, py = pupil(300)
+        segs, seg_len = segments(lens, 300, mono)
+        same_bits(launch_segments(torch, off, segs, seg_len, px, py, False),
+                  launch_segments(torch, dl, segs, seg_len, px, py, False), "unseeded against seeded")
 
 
 @pytest.mark.parametrize("mono", [True, False], ids=["mono", "rows"])
@@ -229,47 +160,46 @@ def test_bit_leaves_results_alone(torch, lenses, name, mono):
     a producer that does not know the bit runs) gives the bits it gives with the bit set."""
     lens, dl = lenses[name][mono]
     n = 4099
-    px, py = _pupil(n)
-    segs, seg_len = _segments(lens, n, mono)
-    on = _launch(torch, dl, segs, seg_len, px, py, False)
+    px, py = pupil(n)
+    segs, seg_len = segments(lens, n, mono)
+    on = launch_segments(torch, dl, segs, seg_len, px, py, False)
     flags = dl.c.form_flags
-    assert _selected(dl)
+    assert selected(dl)
     dl.c.form_flags = 0
     try:
-        off = _launch(torch, dl, segs, seg_len, px, py, False)
+        off = launch_segments(torch, dl, segs, seg_len, px, py, False)
     finally:
         dl.c.form_flags = flags
-    _same_bits(on, off, f"{name} spheres bit on / off")
+    same_bits(on, off, f"{name} spheres bit on / off")
 
 
-def _through_the_new_form(monkeypatch):
-    """test_gpu_closed_sphere_seeds.py's cases with one more assertion in their check: the
-    lens they trace selects the all-spheres form."""
+def _through_the_new_form():
+    """-> (check, seen): test_gpu_closed_sphere_seeds.py's check with one more assertion, that
+    the lens a case traces selects the all-spheres form, and the lenses it has seen."""
     seen = []
 
     def check(torch, dl, *args, **kw):
-        assert _selected(dl), "the case's lens does not select the all-spheres form"
+        assert selected(dl), "the case's lens does not select the all-spheres form"
         seen.append(dl)
-        return _check_generated(torch, dl, *args, **kw)
+        return check_generated(torch, dl, *args, **kw)
 
-    monkeypatch.setattr(seeds, "_check_generated", check)
-    return seen
+    return check, seen
 
 
-def test_vertex_and_rim_hits(torch, monkeypatch):
+def test_vertex_and_rim_hits(torch):
     """A ray at the vertex (through +-0) and hits down the rim to 1 - q = 2^-53 and past 0:
     the operand set of test_gpu_closed_sphere_seeds.py."""
-    seen = _through_the_new_form(monkeypatch)
-    seeds.test_vertex_and_rim_hits(torch)
+    check, seen = _through_the_new_form()
+    vertex_and_rim_case(torch, check)
     assert seen
 
 
 @pytest.mark.parametrize("hy", [0.0, 1.0])
 @pytest.mark.parametrize("exp", [140, -140])
-def test_scaled_singlets(torch, pupils, monkeypatch, exp, hy):  # noqa: F811
+def test_scaled_singlets(torch, pupils, exp, hy):
     """Every length times 2^+-140 (the same file's operand set)."""
-    seen = _through_the_new_form(monkeypatch)
-    seeds.test_scaled_singlets(torch, pupils, exp, hy)
+    check, seen = _through_the_new_form()
+    scaled_singlets_case(torch, pupils, exp, hy, check)
     assert seen
 
 
@@ -281,17 +211,17 @@ def test_extreme_pupil_operands(torch, lenses, name):
     from optiland_pr_amd.lowering import segment_params
 
     lens, dl = lenses[name][True]
-    assert _selected(dl)
+    assert selected(dl)
     hard = [5e-324, -5e-324, 2.0**-1040, 2.0**-1022, 2.0**-300, -(2.0**-300), 2.0**-301,
             2.0**300, -(2.0**300), 2.0**301, 2.0**1000, np.inf, -np.inf, np.nan, -0.0, 0.0]
     pts = [(a, b) for a in hard for b in (0.0, -0.0, 0.3)] + [(0.3, a) for a in hard]
     pts += [(a, a) for a in hard]
-    px, py = _pupil(4 * len(pts))  # ordinary rays, three quarters of the case
+    px, py = pupil(4 * len(pts))  # ordinary rays, three quarters of the case
     k = np.arange(len(pts)) * 4 + 1  # spread over the waves, never ray 0
     px[k], py[k] = np.array(pts, dtype=np.float64).T
     seg = segment_params(lens, 0.0, 0.7, 0)
     with np.errstate(all="ignore"):
-        got = _check_generated(torch, dl, seg, px, py, f"{name} extreme operands", LENSES[name][0])
+        got = check_generated(torch, dl, seg, px, py, f"{name} extreme operands", LENSES[name][0])
     ordinary = np.ones(px.size, bool)
     ordinary[k] = False
     assert np.isfinite(got["x"][ordinary]).all()

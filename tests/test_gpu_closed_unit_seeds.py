@@ -16,91 +16,16 @@ import dataclasses
 import numpy as np
 import pytest
 
+from tests._closed import (CONIC, HALF_BALL, N_ORACLE, check_generated, launch, optic,
+                           pupils_fixture, same_bits, scaled_singlet)
+from tests._closed import torch  # noqa: F401
 from tests._plain_lenses import PLAIN, build
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "z", "L", "M", "N", "i", "opd")
-N_ORACLE = 4099
-N_PUPIL = 1 << 16
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-
-    if not t.cuda.is_available():
-        pytest.fail("GPU tests need the MI355X (torch.cuda.is_available() is False)")
-    from optiland_pr_amd import _native
-
-    _native.load()
-    return t
-
-
-def _same_bits(got, exp, what):
-    for a in FIELDS:
-        g, e = np.asarray(got[a]), np.asarray(exp[a])
-        np.testing.assert_array_equal(g.view(np.uint64), e.view(np.uint64), err_msg=f"{what} {a}")
-
-
-def _same_as_oracle(got, ref, what, sel=slice(None)):
-    for a in FIELDS:
-        g, r = np.asarray(got[a])[sel], np.asarray(getattr(ref, a))
-        np.testing.assert_array_equal(np.isnan(g), np.isnan(r), err_msg=f"{what} {a} NaN")
-        ok = ~np.isnan(r)
-        if a == "i":
-            with np.errstate(all="ignore"):
-                np.testing.assert_allclose(g[ok], r[ok], rtol=1e-12, atol=0)
-            continue
-        np.testing.assert_array_equal(g[ok], r[ok], err_msg=f"{what} {a}")
-        np.testing.assert_array_equal(np.signbit(g[ok]), np.signbit(r[ok]),
-                                      err_msg=f"{what} sign of {a}")
-
-
-@pytest.fixture(scope="module")
-def pupils():
-    """name -> (px, py): one seed of 2^16 random pupil points and the uniform 129 grid,
-    whose centre column and row are +0 (sdiv0's zero numerator over the seeded divisor)."""
-    from optiland_pr_amd.distribution import RandomDistribution, UniformDistribution
-
-    d = RandomDistribution(seed=4)
-    d.generate_points(N_PUPIL)
-    out = {"seed4": (d.x.copy(), d.y.copy())}
-    d = UniformDistribution()
-    d.generate_points(129)
-    out["uniform129"] = (np.ascontiguousarray(d.x), np.ascontiguousarray(d.y))
-    assert np.any((out["uniform129"][1] == 0.0) & ~np.signbit(out["uniform129"][1]))
-    return out
-
-
-def _launch(torch, dl, seg, px, py, exact, wl):
-    from optiland_pr_amd.raytrace import RealRays, trace_pupil
-
-    n = px.size
-    out = RealRays.empty(n, wl)
-    trace_pupil(dl, np.stack([seg]), torch.as_tensor(px, device="cuda"),
-                torch.as_tensor(py, device="cuda"), out, n, n, n, exact_only=exact)
-    torch.cuda.synchronize()
-    return out.numpy()
-
-
-def _check_generated(torch, dl, seg, px, py, what, wl=0.55, min_finite=0.5):
-    """Default launch against ORT_OPT_EXACT and (at most N_ORACLE rays) the oracle."""
-    from oracle import trace_np
-    from optiland_pr_amd import _abi
-
-    assert dl.c.frame_flags == _abi.LENS_AXIAL | _abi.LENS_PLAIN, what  # the plain kernels
-    px, py = np.ascontiguousarray(px, dtype=np.float64), np.ascontiguousarray(py, dtype=np.float64)
-    fast = _launch(torch, dl, seg, px, py, False, wl)
-    _same_bits(fast, _launch(torch, dl, seg, px, py, True, wl), what)
-    n = px.size
-    sel = np.arange(N_ORACLE) * (n // N_ORACLE) if n > N_ORACLE else np.arange(n)
-    with np.errstate(all="ignore"):
-        ref = trace_np.trace_segment(dl.table, trace_np.generate_rays(seg, px[sel], py[sel]),
-                                     int(seg["lambda_idx"])).rays
-    _same_as_oracle(fast, ref, what, sel)
-    assert np.isfinite(fast["x"]).mean() > min_finite, what
-    return fast
+# one seed of 2^16 random pupil points and the uniform 129 grid, whose centre column and row
+# are +0 (sdiv0's zero numerator over the seeded divisor)
+pupils = pupils_fixture(1 << 16, seeds=(4,), grids=(129,))
 
 
 @pytest.mark.parametrize("hy", [0.0, 0.7, 1.0])
@@ -116,46 +41,7 @@ def test_sample_objectives(torch, pupils, name, hy):
     assert np.any(f & _abi.SURF_TWO_INV_R)
     seg = segment_params(lens, 0.0, hy, 0)
     for pname, (px, py) in pupils.items():
-        _check_generated(torch, dl, seg, px, py, f"{name} hy={hy} {pname}", wl)
-
-
-def _optic(rows, scale=1.0, epd=10.0, fields=(0.0,)):
-    """A centred lens from add_surface rows; radii, thicknesses and the entrance pupil
-    diameter times scale."""
-    from optiland_pr_amd.optic import Optic
-
-    lens = Optic()
-    for i, row in enumerate(rows):
-        kw = dict(row)
-        for key in ("radius", "thickness"):
-            if key in kw and np.isfinite(kw[key]):
-                kw[key] = kw[key] * scale
-        lens.add_surface(index=i, **kw)
-    lens.set_aperture(aperture_type="EPD", value=epd * scale)
-    lens.set_field_type(field_type="angle")
-    for y in fields:
-        lens.add_field(y=y)
-    lens.add_wavelength(value=0.55, is_primary=True)
-    return lens
-
-
-_CONIC = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=22.01359, thickness=3.25896, material="SK16", conic=-0.6),
-    dict(radius=-435.76044, thickness=6.00755),
-    dict(radius=-22.21328, thickness=0.99997, material=("F2", "schott")),
-    dict(radius=20.29192, thickness=4.75041, is_stop=True, conic=0.8),
-    dict(radius=79.68360, thickness=2.95208, material="SK16"),
-    dict(radius=-18.39533, thickness=42.20778, conic=1.2),
-    dict(),
-]
-# unit radii: scaled by s, the front radius is s itself
-_SINGLET = [
-    dict(radius=np.inf, thickness=np.inf),
-    dict(radius=1.0, thickness=0.25, material="SK16", is_stop=True),
-    dict(radius=-1.0, thickness=2.0),
-    dict(),
-]
+        check_generated(torch, dl, seg, px, py, f"{name} hy={hy} {pname}", wl)
 
 
 @pytest.mark.parametrize("hy", [0.0, 1.0])
@@ -164,26 +50,14 @@ def test_conic_constants(torch, pupils, hy):
     from optiland_pr_amd.lowering import segment_params
     from optiland_pr_amd.raytrace import lens_for
 
-    lens = _optic(_CONIC, fields=(0.0, 10.0))
+    lens = optic(CONIC, fields=(0.0, 10.0))
     dl = lens_for(lens, [0.55])
     assert np.count_nonzero(dl.table.surfaces["conic"]) == 3
     px, py = pupils["seed4"]
-    _check_generated(torch, dl, segment_params(lens, 0.0, hy, 0), px[:8192], py[:8192],
-                     f"conic hy={hy}")
+    check_generated(torch, dl, segment_params(lens, 0.0, hy, 0), px[:8192], py[:8192],
+                    f"conic hy={hy}")
     px, py = pupils["uniform129"]
-    _check_generated(torch, dl, segment_params(lens, 0.0, hy, 0), px, py, f"conic grid hy={hy}")
-
-
-def _scaled_singlet(scale, hy):
-    """-> (lens with every length times scale, its segment). The segment is the unit
-    lens's with its lengths times scale (a power of two: exact), so that the pupil
-    machinery never sees the extreme values."""
-    from optiland_pr_amd.lowering import segment_params
-
-    seg = segment_params(_optic(_SINGLET, 1.0, epd=0.24, fields=(0.0, 3.0)), 0.0, hy, 0).copy()
-    for key in ("epd", "epl", "x_off", "y_off", "z0"):
-        seg[key] = seg[key] * scale
-    return _optic(_SINGLET, scale, epd=0.24, fields=(0.0, 3.0)), seg
+    check_generated(torch, dl, segment_params(lens, 0.0, hy, 0), px, py, f"conic grid hy={hy}")
 
 
 @pytest.mark.parametrize("hy", [0.0, 1.0])
@@ -195,13 +69,13 @@ def test_scaled_singlet(torch, pupils, exp, hy):
     from optiland_pr_amd.raytrace import lens_for
 
     scale = 2.0**exp
-    lens, seg = _scaled_singlet(scale, hy)
+    lens, seg = scaled_singlet(scale, hy)
     dl = lens_for(lens, [0.55])
     s = dl.table.surfaces
     assert np.all(s["flags"][:2] & _abi.SURF_TWO_INV_R)
     np.testing.assert_array_equal(s["norm_radius"][:2], [2.0 / scale, -2.0 / scale])
     px, py = pupils["seed4"]
-    _check_generated(torch, dl, seg, px[:N_ORACLE], py[:N_ORACLE], f"singlet 2^{exp} hy={hy}")
+    check_generated(torch, dl, seg, px[:N_ORACLE], py[:N_ORACLE], f"singlet 2^{exp} hy={hy}")
 
 
 @pytest.mark.parametrize("which", ["all", "every_other"])
@@ -223,9 +97,9 @@ def test_tables_without_the_bit(torch, pupils, name, which):
     assert off.c.frame_flags == dl.c.frame_flags
     seg = segment_params(lens, 0.0, 0.7, 0)
     px, py = pupils["uniform129"]
-    _same_bits(_launch(torch, dl, seg, px, py, False, wl),
-               _launch(torch, off, seg, px, py, False, wl), f"{name} bit cleared on {which}")
-    _check_generated(torch, off, seg, px[:N_ORACLE], py[:N_ORACLE], f"{name} cleared {which}", wl)
+    same_bits(launch(torch, dl, seg, px, py, False, wl),
+              launch(torch, off, seg, px, py, False, wl), f"{name} bit cleared on {which}")
+    check_generated(torch, off, seg, px[:N_ORACLE], py[:N_ORACLE], f"{name} cleared {which}", wl)
 
 
 def test_rim_and_vertex_hits(torch):
@@ -237,13 +111,7 @@ def test_rim_and_vertex_hits(torch):
     from optiland_pr_amd.lowering import segment_params
     from optiland_pr_amd.raytrace import lens_for
 
-    rows = [
-        dict(radius=np.inf, thickness=np.inf),
-        dict(radius=5.0, thickness=6.0, material="SK16", is_stop=True),
-        dict(radius=-40.0, thickness=20.0),
-        dict(),
-    ]
-    lens = _optic(rows)
+    lens = optic(HALF_BALL)
     dl = lens_for(lens, [0.55])
     seg = segment_params(lens, 0.0, 0.0, 0)
     assert float(seg["epd"]) == 2.0 * 5.0 and float(seg["x_off"]) == 0.0
@@ -261,7 +129,7 @@ def test_rim_and_vertex_hits(torch):
     for p in (1.0, np.nextafter(1.0, 2.0), 1.0 + 2.0**-20, 1.5):
         pts += [(p, 0.0), (0.0, -p), (-p * 0.6, p * 0.8)]
     px, py = (np.array(c, dtype=np.float64) for c in zip(*pts))
-    got = _check_generated(torch, dl, seg, px, py, "rim and vertex", min_finite=0.0)
+    got = check_generated(torch, dl, seg, px, py, "rim and vertex", min_finite=0.0)
     assert np.isfinite(got["x"][n_vertex:n_pass]).all()  # the fan passes
     assert np.isfinite(got["x"][:n_vertex]).any()
     assert np.isnan(got["x"][px * px + py * py > 1.0 + 2.0**-19]).all()  # the misses

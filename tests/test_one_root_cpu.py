@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import trace_np
-from tests.test_seed_sequences_cpu import fma
+from tests._fast_sequences import fma
 
 C_GUARD = 1.0 + 2.0**-20  # kOneRootC
 T_GUARD = 2.0**-300

@@ -6,55 +6,13 @@ normal_conic_rcp<true>), restated operation for operation with an exact fma
 RN(2 / R); v_rsq is modelled as (1 + e0) / sqrt(x) rounded, e0 = +-2^-20. Each quotient
 formed from such a reciprocal must be NumPy's division, bit for bit.
 """
-import math
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests._fast_sequences import fma, numerators, quot, sqrt_h
 from tests._plain_lenses import NOT_PLAIN, PLAIN, build
-
-
-def rn(v):
-    """A Fraction rounded to the nearest double, ties to even (int / int is exact)."""
-    return v.numerator / v.denominator
-
-
-def fma(a, b, c):
-    return rn(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def quot(a, b, y):  # ort_fastpath.h quot
-    q0 = a * y
-    r = fma(-b, q0, a)
-    return fma(r, y, q0)
-
-
-def _numerators(rng, n):
-    return np.ldexp(rng.uniform(1.0, 2.0, n), rng.integers(-300, 300, n)) * rng.choice([-1.0, 1.0], n)
-
-
-def _rsq_model(x, e0):
-    """(1 + e0) / sqrt(x) rounded: sqrt to 120 bits past the quotient's."""
-    f = Fraction(x)
-    k = 200
-    s = Fraction(math.isqrt(f.numerator * f.denominator << (2 * k)), f.denominator << k)
-    return rn((1 + Fraction(e0)) / s)
-
-
-def sqrt_h(x, e0):
-    """ort_fastpath.h sqrt_h: -> (g, h)."""
-    y = _rsq_model(x, e0)
-    g = x * y
-    h = y * 0.5
-    r = fma(-h, g, 0.5)
-    g = fma(g, r, g)
-    h = fma(h, r, h)
-    d = fma(-g, g, x)
-    g = fma(d, h, g)
-    d = fma(-g, g, x)
-    g = fma(d, h, g)
-    return g, h
 
 
 def test_two_inv_r_h_quotients_are_ieee():
@@ -64,7 +22,7 @@ def test_two_inv_r_h_quotients_are_ieee():
     xs += [float(v) for v in rng.uniform(0.0, 1.0, 40)]
     radii = [22.01359, -435.76044, 1.0, -1.0, 3.0, 2.0**150, -(2.0**150), 2.0**-150,
              -(2.0**-150), 2.0**150 * (1 - 2.0**-53), 2.0**-150 * (1 + 2.0**-52)]
-    radii += [float(v) for v in _numerators(rng, 12) if 2.0**-150 <= abs(v) <= 2.0**150]
+    radii += [float(v) for v in numerators(rng, 12) if 2.0**-150 <= abs(v) <= 2.0**150]
     for x in xs:
         for e0 in (2.0**-20, -(2.0**-20)):
             g, h = sqrt_h(x, e0)
@@ -78,7 +36,7 @@ def test_two_inv_r_h_quotients_are_ieee():
                 e = fma(-denom, y0, 1.0)
                 y = fma(y0, e, y0)
                 assert abs(Fraction(denom) * Fraction(y) - 1) <= Fraction(1, 2**52), (x, R)
-                for n in _numerators(rng, 6):
+                for n in numerators(rng, 6):
                     n = float(n)
                     exp = float(np.float64(n) / np.float64(denom))  # |exp| in 2^-451 .. 2^478
                     assert quot(n, denom, y) == exp, (x, e0, R, n)

@@ -17,33 +17,13 @@ from fractions import Fraction
 
 import numpy as np
 
-from tests.test_seed_sequences_cpu import _numerators, fma, quot, sqrt_h
+from tests._fast_sequences import fma, numerators, quot, quot_pos, sqrt_h, sqrt_seeded_h
 
 SEED_BOUND = Fraction(1, 2**50)  # the bound at normal_conic_rcp's sphere branch
 Q_TARGETS = [0.0, 2.0**-60, 0.25, 0.9, 1 - 2.0**-10, 1 - 2.0**-40, 1 - 2.0**-52]
 RADII = [22.01359, -435.76044, 1.0, -3.0, 2.0**150, -(2.0**150), 2.0**-150, -(2.0**-150),
          2.0**140 * 1.37, -(2.0**-140) * 1.91]
 DIRS = [(1.0, 0.0), (0.0, -1.0), (0.6, -0.8)]
-
-
-def quot_pos(a, b, y):  # ort_fastpath.h quot_pos
-    q0 = a * y
-    rn_ = fma(b, q0, -a)
-    return fma(-rn_, y, q0)
-
-
-def sqrt_seeded_h(x, y):
-    """ort_fastpath.h sqrt_seeded_h: the Goldschmidt sequence from the seed y -> (g, h)."""
-    g = x * y
-    h = y * 0.5
-    r = fma(-h, g, 0.5)
-    g = fma(g, r, g)
-    h = fma(h, r, h)
-    d = fma(-g, g, x)
-    g = fma(d, h, g)
-    d = fma(-g, g, x)
-    g = fma(d, h, g)
-    return g, h
 
 
 def _w_of(x, y, R):
@@ -170,7 +150,7 @@ def test_unit_reciprocal():
         # the seed: (1 - (1 - a)^2) / a and the rounding of 2 - a
         assert abs(Fraction(a) * Fraction(y0) - 1) < Fraction(1, 2**52), a
         assert abs(Fraction(a) * Fraction(y) - 1) <= Fraction(1, 2**52), a
-        for n in _numerators(rng, 6):
+        for n in numerators(rng, 6):
             n = float(n)
             assert quot_pos(n, a, y) == _ieee_div(n, a), (a, n)
 

@@ -1,11 +1,14 @@
 """Per-kernel ISA statistics of built objects (measurement tooling, not product).
 
-usage: python tools/isa_stats.py [FILE.o|FILE.so ...] [--filter SUBSTR] [--dump DIR]
+usage: python tools/isa_stats.py [FILE.o|FILE.so ...] [--filter SUBSTR] [--dump DIR] [--digest]
 Default: every object under optiland_pr_amd/lib/obj/. For each kernel prints the
 instruction count, VGPR / AGPR / SGPR counts and scratch bytes (from the code object's
-metadata notes), and with --dump writes the disassembly per object.
+metadata notes), and with --dump writes the disassembly per object. --digest prints
+instead one line per object: the SHA-256 of its gfx950 code object (equal lines before and
+after a change of the kernel headers: the device code is the same, byte for byte).
 """
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -59,6 +62,7 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     filt = sys.argv[sys.argv.index("--filter") + 1] if "--filter" in sys.argv else ""
     dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+    digest = "--digest" in sys.argv
     if filt in args:
         args.remove(filt)
     if dump in args:
@@ -70,6 +74,10 @@ def main():
                 co = code_objects(f, tmp)
             except subprocess.CalledProcessError:
                 continue  # no device code in this object
+            if digest:
+                with open(co, "rb") as fh:
+                    print(f"{hashlib.sha256(fh.read()).hexdigest()}  {os.path.basename(f)}")
+                continue
             dis, counts, meta = stats(co)
             if dump:
                 os.makedirs(dump, exist_ok=True)
