@@ -114,6 +114,19 @@ int ort_host_irradiance_bin_vjp(const double* x, const double* y, const double* 
 int ort_host_dft_psf(const double* amp, const double* opd_waves, int64_t batch, int64_t n,
                      int64_t m, double pad, double* out);
 
+/* ort_sampled_otf on host memory (added within v3): the kernel's own term
+ * (csrc/ort_sampled_otf.h) in the kernel's order -- per (batch entry, frequency) the pupil in
+ * chunks of ORT_SAMPLED_OTF_CHUNK points, each chunk's terms added as the workgroup adds
+ * them (64 lanes pairwise: neighbours, pairs of neighbours, ...; then the four groups of 64
+ * in index order from zero), the chunk sums in chunk order from zero -- OpenMP over the
+ * (batch entry, frequency) pairs (the value does not depend on the thread count). Same
+ * argument checks as ort_sampled_otf, no workspace. */
+int ort_host_sampled_otf(const double* x, const double* y, int64_t n_pupil,
+                         const double* intensity, const double* opd_waves, int64_t n_batch,
+                         const ort_zernike_term* terms, const double* radial,
+                         const double* coeffs, int64_t n_terms, const double* shift_x,
+                         const double* shift_y, int64_t n_freq, double* otf);
+
 /* ort_trace_pupil_polarized / ort_trace_sequential_polarized on host memory (added within
  * v3): the kernels' per-ray polarization code (csrc/ort_polar.h) inside the host trace, so
  * the ray geometry is ort_host_trace_pupil's / ort_host_trace_sequential's bit for bit.

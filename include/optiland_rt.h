@@ -1033,6 +1033,38 @@ int64_t ort_dft_workspace_size(int64_t batch, int64_t n, int64_t m);
 int ort_dft_psf(const double* amp, const double* opd_waves, int64_t batch, int64_t n, int64_t m,
                 double pad, double* out, void* workspace, int64_t workspace_size, void* stream);
 
+/* ---- SampledMTF's overlap sum (mtf/sampled.py:162-205; added within v21: new entry point
+ * only) ----------------------------------------------------------------------------------
+ * The OTF at n_freq pupil shears of n_batch pupils over the same n_pupil sample points, each
+ * pupil sheared against the Zernike polynomial W_b fitted to its own OPD:
+ *   otf[b][f] = sum_j [r_jf <= 1] I_bj exp(2 pi i (opd_bj - W_b(x_j - sx_f, y_j - sy_f)))
+ *   r_jf = sqrt((x_j - sx_f)^2 + (y_j - sy_f)^2), every operation rounded as NumPy rounds it
+ * (the mask agrees with the reference's bit for bit), everything in normalised pupil units
+ * and waves, fp64 throughout, the phase reduced in cycles before the sincos
+ * (csrc/ort_sampled_otf.h). W_b = sum_t coeffs[b][t] norm_t R_t(r) {cos | sin}(|m_t| phi) over
+ * one term structure shared by the batch: `terms` are n_terms ort_zernike_term records (c is
+ * not read) whose a_k lie at radial[rad_off .. rad_off + n_rad), highest power first.
+ * The pupil is summed in fixed chunks of ORT_SAMPLED_OTF_CHUNK points, one lane per point
+ * and one workgroup per (b, f, chunk), its complex sum reduced in a fixed order into the
+ * workspace; a second launch adds each (b, f)'s chunk sums in chunk order. No atomics: the
+ * bits do not depend on the run, nor on which other frequencies or batch entries share the
+ * call. */
+#define ORT_SAMPLED_OTF_CHUNK 256
+
+/* Bytes of device workspace ort_sampled_otf needs (< 0: ORT_ERR_ARG). */
+int64_t ort_sampled_otf_workspace_size(int64_t n_batch, int64_t n_freq, int64_t n_pupil);
+
+/* x, y: [n_pupil]; intensity, opd_waves: [n_batch][n_pupil]; coeffs: [n_batch][n_terms];
+ * shift_x, shift_y: [n_freq]; otf: [n_batch][n_freq][2] (re, im); all device memory.
+ * n_pupil == 0 writes zeros; n_batch == 0 or n_freq == 0 launches nothing. ORT_ERR_ARG for a
+ * negative count, a null pointer of a positive count or a short workspace. Two launches on
+ * `stream`, no synchronisation. */
+int ort_sampled_otf(const double* x, const double* y, int64_t n_pupil, const double* intensity,
+                    const double* opd_waves, int64_t n_batch, const ort_zernike_term* terms,
+                    const double* radial, const double* coeffs, int64_t n_terms,
+                    const double* shift_x, const double* shift_y, int64_t n_freq, double* otf,
+                    void* workspace, int64_t workspace_size, void* stream);
+
 /* Ray generation only (ray_generator.py:28-106): fills rays_out from pupil points. */
 int ort_generate_rays(const double* px, const double* py, ort_rays* rays_out,
                       const ort_batch* batch, void* stream);

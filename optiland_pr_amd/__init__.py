@@ -8,15 +8,19 @@ SurfaceGroup / RealRays / SpotDiagram / Wavefront interface.
 
 from . import _abi
 from . import ops  # noqa: F401  (registers torch.ops.ort.trace_sequential / trace_pupil / huygens_psf /
-# dft_psf / irradiance_bin)
+# dft_psf / sampled_otf / irradiance_bin)
 from .distribution import create_distribution
 from .irradiance import IncoherentIrradiance
 from .materials import IdealMaterial, Material
-from .mtf import FFTMTF
+from .analysis import ZernikeOPD
+from .mtf import FFTMTF, SampledMTF
 from .optic import Optic
 from .psf import FFTPSF, MMDFTPSF, HuygensPSF
+from .through_focus import ThroughFocusMTF
+from .zernike import ZernikeFit, ZernikeFringe, ZernikeNoll, ZernikeStandard
 
 __all__ = ["Optic", "IdealMaterial", "Material", "HuygensPSF", "FFTPSF", "MMDFTPSF", "FFTMTF",
-           "IncoherentIrradiance",
+           "IncoherentIrradiance", "SampledMTF", "ThroughFocusMTF", "ZernikeOPD", "ZernikeFit",
+           "ZernikeStandard", "ZernikeFringe", "ZernikeNoll",
            "create_distribution", "_abi"]
 __version__ = "0.1.0"

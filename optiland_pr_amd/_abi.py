@@ -14,6 +14,7 @@ HUYGENS_CHUNK = 512  # ORT_HUYGENS_CHUNK: pupil points per partial sum of ort_hu
 DFT_TILE_M = 256  # ORT_DFT_TILE_M: columns u per thread-column step of ort_dft_psf
 DFT_TILE_K = 32  # ORT_DFT_TILE_K: the sum chunk (and stage A's row tile) of ort_dft_psf
 DFT_MAX_SIZE = 32768  # ORT_DFT_MAX_SIZE: the largest pupil or image edge
+SAMPLED_OTF_CHUNK = 256  # ORT_SAMPLED_OTF_CHUNK: pupil points per partial sum of ort_sampled_otf
 BIN_HISTOGRAM = 0  # ort_bin_mode
 BIN_BILINEAR = 1
 IRRADIANCE_TILE_PIXELS = 16384  # ORT_IRRADIANCE_TILE_PIXELS: the largest image summed in LDS

@@ -227,6 +227,9 @@ DEVICE_PROTOTYPES = {
                                   PTR, PTR, I64, PTR]),
     "ort_dft_workspace_size": (I64, [I64, I64, I64]),
     "ort_dft_psf": (C.c_int, [PTR, PTR, I64, I64, I64, F64, PTR, PTR, I64, PTR]),
+    "ort_sampled_otf_workspace_size": (I64, [I64, I64, I64]),
+    "ort_sampled_otf": (C.c_int, [PTR, PTR, I64, PTR, PTR, I64, PTR, PTR, PTR, I64, PTR, PTR, I64,
+                                  PTR, PTR, I64, PTR]),
     "ort_irradiance_workspace_size": (I64, [I64, I64]),
     "ort_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64, PTR, PTR,
                                      I64, PTR]),
@@ -260,6 +263,8 @@ HOST_PROTOTYPES = {
     "ort_host_huygens_psf": (C.c_int, [PTR, PTR, PTR, I64, PTR, PTR, PTR, PTR, PTR, I64, F64,
                                        F64, PTR]),
     "ort_host_dft_psf": (C.c_int, [PTR, PTR, I64, I64, I64, F64, PTR]),
+    "ort_host_sampled_otf": (C.c_int, [PTR, PTR, I64, PTR, PTR, I64, PTR, PTR, PTR, I64, PTR, PTR,
+                                       I64, PTR]),
     "ort_host_irradiance_bin": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, I32, F64,
                                           PTR]),
     "ort_host_irradiance_bin_vjp": (C.c_int, [PTR, PTR, PTR, I64, PTR, I64, PTR, I64, F64, PTR,

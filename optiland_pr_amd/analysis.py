@@ -21,6 +21,7 @@ from .distribution import BaseDistribution, create_distribution
 from .pupil import pupil_arrays
 from .lowering import pupil_scalars, segment_params
 from .raytrace import RealRays, lens_for, trace_pupil
+from .zernike import ZernikeFit
 
 try:
     import torch
@@ -639,3 +640,22 @@ class OPD(Wavefront):
             raise ValueError("No valid rays with non-zero intensity for RMS calculation.")
         opd = data.opd[mask]
         return torch.sqrt(torch.mean(opd**2))
+
+
+class ZernikeOPD(ZernikeFit, OPD):
+    """wavefront/zernike_opd.py:21-82: the OPD map on the hexapolar distribution (traced and
+    reduced on the device), then the Zernike fit of its points of positive intensity. The
+    attributes of both bases: get_data / rms of OPD; x, y, z, radius, phi, num_pts, zernike,
+    coeffs of ZernikeFit (one read-back of the masked points, the fit on the host)."""
+
+    def __init__(self, optic, field, wavelength, num_rings=15, zernike_type="fringe",
+                 num_terms=37, strategy="chief_ray", remove_tilt=False, **kwargs):
+        OPD.__init__(self, optic=optic, field=field, wavelength=wavelength, num_rays=num_rings,
+                     distribution="hexapolar", strategy=strategy, remove_tilt=remove_tilt,
+                     **kwargs)
+        data = self.get_data(self.fields[0], self.wavelengths[0])
+        z = data.opd
+        mask = data.intensity > 0
+        x = torch.as_tensor(np.asarray(self.distribution.x, dtype=np.float64), device=z.device)
+        y = torch.as_tensor(np.asarray(self.distribution.y, dtype=np.float64), device=z.device)
+        ZernikeFit.__init__(self, x[mask], y[mask], z[mask], zernike_type, num_terms)

@@ -29,14 +29,14 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "ort_k_trace_w.hip", "ort_k_vjp.hip", "ort_k_vjp1.hip", "ort_k_vjp2.hip", "ort_k_vjp4.hip", "ort_k_geom.hip",
     "ort_k_adj.hip", "ort_k_adj2.hip", "ort_k_adj4.hip", "ort_k_adj2r.hip", "ort_k_adj4r.hip", "ort_k_pupil.hip", "ort_k_trace_ia.hip",
     "ort_k_spot.hip", "ort_k_wavefront.hip", "ort_k_huygens.hip", "ort_k_irradiance.hip",
-    "ort_k_dft.hip",
+    "ort_k_dft.hip", "ort_k_sampled_otf.hip",
     "ort_k_trace_pol.hip", "ort_k_trace_scat.hip", "ort_k_ensemble.hip")]
 HEADERS = [os.path.join(CSRC, "ort_core.h"), os.path.join(CSRC, "ort_args.h"), os.path.join(CSRC, "ort_kernels.h"), os.path.join(CSRC, "ort_fastpath.h"),
            os.path.join(CSRC, "ort_adjoint.h"), os.path.join(CSRC, "ort_pupil.h"),
            os.path.join(CSRC, "ort_sincos_table.h"), os.path.join(CSRC, "ort_material.h"), os.path.join(CSRC, "ort_interact.h"), os.path.join(CSRC, "ort_reduce.h"),
            os.path.join(CSRC, "ort_sweep.h"), os.path.join(CSRC, "ort_nurbs.h"),
            os.path.join(CSRC, "ort_huygens.h"), os.path.join(CSRC, "ort_irradiance.h"),
-           os.path.join(CSRC, "ort_dft.h"),
+           os.path.join(CSRC, "ort_dft.h"), os.path.join(CSRC, "ort_sampled_otf.h"),
            os.path.join(CSRC, "ort_polar.h"), os.path.join(CSRC, "ort_scatter.h"),
            os.path.join(REPO, "include", "optiland_rt.h")]
 DEPS = SOURCES + HEADERS
@@ -45,7 +45,7 @@ HOST_DEPS = HOST_SOURCES + [os.path.join(CSRC, f) for f in ("ort_core.h", "ort_a
                                                            "ort_material.h", "ort_interact.h",
                                                            "ort_nurbs.h", "ort_huygens.h", "ort_dft.h",
                                                            "ort_irradiance.h", "ort_polar.h",
-                                                           "ort_scatter.h")] + [
+                                                           "ort_scatter.h", "ort_sampled_otf.h")] + [
     os.path.join(REPO, "include", "optiland_rt.h"), os.path.join(REPO, "include", "optiland_host.h")]
 # the host build keeps the kernels' rounding: no contraction of a*b+c (as -ffp-contract=off
 # on hipcc), no fast-math

@@ -327,6 +327,25 @@ inline int dft_check(const double* amp, const double* opd, int64_t batch, int64_
   return ORT_OK;
 }
 
+// ort_sampled_otf / ort_host_sampled_otf: the checks both libraries make (the device adds
+// its workspace and grid limits). An empty pupil, term list, batch or frequency list is valid.
+inline int sampled_otf_check(const double* x, const double* y, int64_t n_pupil,
+                             const double* intensity, const double* opd, int64_t n_batch,
+                             const ort_zernike_term* terms, const double* radial,
+                             const double* coeffs, int64_t n_terms, const double* shift_x,
+                             const double* shift_y, int64_t n_freq, const double* otf) {
+  if (n_pupil < 0 || n_batch < 0 || n_terms < 0 || n_freq < 0) return ORT_ERR_ARG;
+  if (n_terms > 0x7fffffff || n_freq > 0x7fffffff) return ORT_ERR_ARG;
+  if (n_pupil > 0 && (!x || !y)) return ORT_ERR_ARG;
+  if (n_pupil > 0 && n_batch > 0 && (!intensity || !opd)) return ORT_ERR_ARG;
+  if (n_terms > 0 && (!terms || !radial)) return ORT_ERR_ARG;
+  if (n_terms > 0 && n_batch > 0 && !coeffs) return ORT_ERR_ARG;
+  if (n_freq > 0 && (!shift_x || !shift_y)) return ORT_ERR_ARG;
+  if (n_freq > 0 && n_batch > 0 && !otf) return ORT_ERR_ARG;
+  if (n_pupil > 0 && n_batch > INT64_MAX / 8 / n_pupil) return ORT_ERR_ARG;
+  return ORT_OK;
+}
+
 // Table lookup n_tab[lam][mat]: a uniform scalar load when the lens is traced at one
 // wavelength (the common case), else a per-lane load of the small L1-resident table.
 ORT_INLINE double tab(const double* t, int n_lambda, int n_mat, int lam, int mat) {

@@ -31,6 +31,7 @@
 #include "ort_dft.h"
 #include "ort_huygens.h"
 #include "ort_irradiance.h"
+#include "ort_sampled_otf.h"
 #include "ort_sweep.h"
 
 namespace {
@@ -710,6 +711,58 @@ int ort_host_dft_psf(const double* amp, const double* opd_waves, int64_t batch, 
                        t[2 * (j * m + u) + 1], sr, si);
         o[v * m + u] = sr * sr + si * si;
       }
+  }
+  return ORT_OK;
+}
+
+// SampledMTF's overlap sum (mtf/sampled.py:162-205) on host memory: the kernel's term
+// (ort_sampled_otf.h) and its order of additions (ort_k_sampled_otf.hip with ort_reduce.h's
+// block sum): a chunk's 256 lane values -- 0.0 past the pupil's end -- are added 64 at a time
+// as the wave's DPP tree adds them (lane i with lane i ^ 1, then pairs, quads, ... : floating-
+// point addition commutes, so the tree's value does not depend on which lane holds it), the
+// four wave sums in index order onto 0.0, the chunk sums in chunk order onto 0.0.
+int ort_host_sampled_otf(const double* x, const double* y, int64_t n_pupil,
+                         const double* intensity, const double* opd_waves, int64_t n_batch,
+                         const ort_zernike_term* terms, const double* radial,
+                         const double* coeffs, int64_t n_terms, const double* shift_x,
+                         const double* shift_y, int64_t n_freq, double* otf) {
+  const int rc = sampled_otf_check(x, y, n_pupil, intensity, opd_waves, n_batch, terms, radial,
+                                   coeffs, n_terms, shift_x, shift_y, n_freq, otf);
+  if (rc != ORT_OK) return rc;
+  const int64_t pairs = n_batch * n_freq;
+  if (pairs == 0) return ORT_OK;
+  constexpr int64_t kC = ORT_SAMPLED_OTF_CHUNK;
+  const int nt =
+      pairs < 2 ? 1 : threads_for(pairs * std::max<int64_t>(n_pupil, 1) * (n_terms + 1));
+#pragma omp parallel for num_threads(nt) schedule(static)
+  for (int64_t p = 0; p < pairs; ++p) {
+    const int64_t b = p / n_freq, f = p - b * n_freq;
+    const double sx = shift_x[f], sy = shift_y[f];
+    double re = 0.0, im = 0.0;
+    int64_t j0 = 0;
+    do {  // (an empty pupil: one empty chunk, as the kernel's grid)
+      double lane[2][kC];
+      for (int64_t k = 0; k < kC; ++k) {
+        const int64_t j = j0 + k;
+        lane[0][k] = lane[1][k] = 0.0;
+        if (j < n_pupil)
+          ort::sampled_otf_term(x[j], y[j], intensity[b * n_pupil + j],
+                                opd_waves[b * n_pupil + j], sx, sy, terms, radial,
+                                coeffs + b * n_terms, (int)n_terms, lane[0][k], lane[1][k]);
+      }
+      for (int q = 0; q < 2; ++q) {
+        double* v = lane[q];
+        for (int64_t w = 0; w < kC; w += 64)
+          for (int64_t stride = 1; stride < 64; stride *= 2)
+            for (int64_t k = w; k < w + 64; k += 2 * stride) v[k] = v[k] + v[k + stride];
+        double s = 0.0;
+        for (int64_t w = 0; w < kC; w += 64) s += v[w];
+        (q == 0 ? re : im) += s;
+      }
+      j0 += kC;
+    } while (j0 < n_pupil);
+    otf[2 * p] = re;
+    otf[2 * p + 1] = im;
   }
   return ORT_OK;
 }

@@ -241,6 +241,22 @@ def dft_psf(amp, opd_waves, batch, n, m, pad):
     return out
 
 
+def sampled_otf(tensors, batch, n_terms, terms, radial):
+    """ort_host_sampled_otf: the complex OTF [batch * F * 2] of contiguous float64 CPU tensors
+    (x, y [N], intensity, opd_waves [batch * N], coeffs [batch * n_terms], shift_x, shift_y
+    [F]); terms: the _abi.ZERNIKE_TERM records and radial their weights (NumPy arrays,
+    ops._otf_terms)."""
+    lib = _native.load_host()
+    x, y, intensity, opd_waves, coeffs, shift_x, shift_y = tensors
+    n, f = x.numel(), shift_x.numel()
+    out = torch.empty(batch * f * 2, dtype=torch.float64)
+    rc = lib.ort_host_sampled_otf(addr(x), addr(y), n, addr(intensity), addr(opd_waves), batch,
+                                  addr(terms), addr(radial), addr(coeffs), n_terms,
+                                  addr(shift_x), addr(shift_y), f, addr(out))
+    _native.check(rc, "ort_host_sampled_otf")
+    return out
+
+
 def irradiance_bin(x, y, power, x_edges, y_edges, mode, pixel_area=0.0):
     """ort_host_irradiance_bin: the flat map [nx * ny] of contiguous float64 CPU tensors
     (histogram: index ix * ny + iy; bilinear: iy * nx + ix)."""

@@ -8,10 +8,15 @@ zero horizontal frequency and the row of zero vertical frequency. Each is the 1-
 PSF's row sums resp. column sums, so that is what is computed -- torch.fft.fft of the
 projection on the device, shifted, absolute value, divided by its own maximum; no 2-D FFT.
 Visualisation (view) is out of scope, as everywhere in this package.
+
+SampledMTF (mtf/sampled.py:17-207): the MTF at a list of arbitrary frequencies without a PSF,
+from the pupil's overlap with its sheared copy -- one fused kernel for the whole list
+(torch.ops.ort.sampled_otf).
 """
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .analysis import Wavefront, get_working_FNO, resolve_fields
@@ -89,3 +94,81 @@ class FFTMTF:
     def _get_mtf_units(self):
         """mtf/fft.py:154-163."""
         return 1 / ((self.num_rays - 1) * self.resolved_wavelength * 1e-3 * self.FNO)
+
+
+def pupil_shears(frequencies, wavelength_um, xpd, xpl):
+    """mtf/sampled.py:158-178 on the host, in the reference's operation order: the shear of
+    the pupil, in normalised pupil units, for each (fx, fy) in cycles / mm:
+    xpl * (wl_mm * f) / (xpd / 2). -> (shift_x, shift_y), float64 arrays [F]."""
+    wl_mm = wavelength_um * 1e-3
+    f = np.asarray([(float(fx), float(fy)) for fx, fy in frequencies],
+                   dtype=np.float64).reshape(-1, 2)
+    half = xpd / 2
+    return xpl * (wl_mm * f[:, 0]) / half, xpl * (wl_mm * f[:, 1]) / half
+
+
+def otf_modulus(otf, otf_at_zero):
+    """mtf/sampled.py:198-203: |otf| / otf_at_zero of [..., 2] (re, im), 0 where otf_at_zero
+    is 0; otf_at_zero broadcasts against otf[..., 0]."""
+    mod = torch.hypot(otf[..., 0], otf[..., 1])
+    zero = otf_at_zero == 0
+    return torch.where(zero, torch.zeros_like(mod), mod / torch.where(zero, 1.0, otf_at_zero))
+
+
+class SampledMTF:
+    """mtf/sampled.py:17-207 on the device: the MTF at arbitrary (fx, fy) as the overlap sum
+    of the pupil with a copy of itself sheared through the Zernike fit of its OPD.
+
+    Attributes as the reference's: optic, field, wavelength, num_rays, distribution,
+    zernike_terms, zernike_type, x_norm, y_norm, opd_waves, intensity (float64 device tensors),
+    xpd, xpl, zernike_fit and otf_at_zero (a 0-dim device tensor). The reference's complex
+    pupil P1 is omitted: the kernel folds exp(i 2 pi opd) and exp(-i 2 pi W) into one
+    exponential and never stores either factor.
+
+    The wavefront is traced and reduced on the device; the constructor reads the OPD back
+    once for the host least-squares fit. calculate_mtf sends every frequency of the list
+    through ONE torch.ops.ort.sampled_otf call (ort_sampled_otf, csrc/ort_k_sampled_otf.hip)
+    and reads the result back once."""
+
+    def __init__(self, optic, field, wavelength, num_rays=128, distribution="uniform",
+                 zernike_terms=37, zernike_type="fringe"):
+        from .zernike import ZernikeFit
+
+        self.optic = optic
+        self.field = field
+        self.wavelength = resolve_wavelength(optic, wavelength)
+        self.num_rays = num_rays
+        self.distribution = distribution
+        self.zernike_terms = zernike_terms
+        self.zernike_type = zernike_type
+
+        wf = Wavefront(optic, fields=[self.field], wavelengths=[self.wavelength],
+                       num_rays=self.num_rays, distribution=self.distribution)
+        data = wf.get_data(self.field, self.wavelength)
+        dev = data.opd.device
+        self.x_norm = torch.as_tensor(np.asarray(wf.distribution.x, dtype=np.float64), device=dev)
+        self.y_norm = torch.as_tensor(np.asarray(wf.distribution.y, dtype=np.float64), device=dev)
+        self.opd_waves = data.opd
+        self.intensity = data.intensity
+
+        self.xpd = self.optic.paraxial.XPD()
+        self.xpl = -self.optic.paraxial.XPL()
+
+        self.zernike_fit = ZernikeFit(self.x_norm, self.y_norm, self.opd_waves,
+                                      self.zernike_type, self.zernike_terms)
+        self.otf_at_zero = torch.sum(self.intensity)
+
+    def calculate_mtf(self, frequencies, as_tensor=False):
+        """mtf/sampled.py:108-207: the MTF at each (fx, fy) in cycles / mm, a list of Python
+        floats (as_tensor=True: the float64 device tensor [F], no read-back)."""
+        freqs = [(float(fx), float(fy)) for fx, fy in frequencies]
+        dev = self.opd_waves.device
+        if self.xpd == 0.0:  # sampled.py:163-168
+            out = [1.0 if fx == 0.0 and fy == 0.0 else 0.0 for fx, fy in freqs]
+            return torch.tensor(out, dtype=torch.float64, device=dev) if as_tensor else out
+        sx, sy = pupil_shears(freqs, self.wavelength, self.xpd, self.xpl)
+        otf = torch.ops.ort.sampled_otf(
+            self.x_norm, self.y_norm, self.intensity, self.opd_waves, self.zernike_fit.coeffs,
+            self.zernike_type, torch.as_tensor(sx, device=dev), torch.as_tensor(sy, device=dev))
+        mtf = otf_modulus(otf, self.otf_at_zero)
+        return mtf if as_tensor else mtf.cpu().tolist()

@@ -44,6 +44,10 @@ wavelength_mm, rp) -> psf is HuygensPSF's summation (psf/huygens_fresnel_strateg
 ort_huygens_psf) on both keys; it has no autograd formula yet and refuses inputs that require
 grad.
 
+ort::sampled_otf(x, y, intensity, opd_waves, coeffs, kind, shift_x, shift_y) -> otf is
+SampledMTF's overlap sum over pupil shears (mtf/sampled.py:162-205, ort_sampled_otf) on both
+keys, forward only like the two PSF ops.
+
 ort::dft_psf(amp, opd_waves, image_size, pad_size) -> psf is the pupil-to-image transform of
 FFTPSF, MMDFTPSF and FFTMTF (psf/fft.py:169-234, psf/mmdft.py:164-184, ort_dft_psf) on both
 keys, of one (n, n) pupil or a batch (B, n, n); it refuses inputs that require grad.
@@ -1095,6 +1099,136 @@ def _dft_backward(ctx, grad):
 
 
 dft_psf.register_autograd(_dft_backward, setup_context=_dft_setup)
+
+
+# --------------------------------------------------------------------------------------
+# ort::sampled_otf -- SampledMTF's overlap sum over pupil shears (mtf/sampled.py:162-205)
+# --------------------------------------------------------------------------------------
+_OTF_KINDS = ("fringe", "standard", "noll")
+_otf_term_cache: dict = {}
+
+
+def _otf_terms(kind, n_terms, device):
+    """The term structure of the first n_terms polynomials of a scheme for ort_sampled_otf:
+    the ort_zernike_term records (c unused) and their radial weights a_k, from
+    geometries._zernike_structure -- as NumPy arrays on the host, as (uint8 records, float64
+    weights) tensors on a device; built once per (scheme, count, device)."""
+    key = (kind, int(n_terms), str(device))
+    hit = _otf_term_cache.get(key)
+    if hit is not None:
+        return hit
+    from .geometries import _zernike_structure
+
+    terms = np.zeros(max(1, n_terms), dtype=_abi.ZERNIKE_TERM)
+    radial = []
+    for j, (norm, n, m, a, _d) in enumerate(_zernike_structure(kind, int(n_terms))):
+        terms[j] = (0.0, norm, n, m, len(radial), len(a))
+        radial.extend(a)
+    radial = np.asarray(radial or [0.0], dtype=np.float64)
+    if torch.device(device).type == "cpu":
+        out = (terms, radial)
+    else:
+        out = (_calls.bytes_tensor(terms).to(device), torch.from_numpy(radial).to(device))
+    _otf_term_cache[key] = out
+    return out
+
+
+def _check_sampled_otf_inputs(x, y, intensity, opd_waves, coeffs, kind, shift_x, shift_y):
+    """The kernels read every array as doubles of one device: x, y of one size N, intensity
+    and opd_waves [N] or [B, N], coeffs [T] or [B, T], two shear arrays of one size.
+    -> (B, N, T, F, batched)."""
+    for t in (x, y, intensity, opd_waves, coeffs, shift_x, shift_y):
+        if t.dtype != torch.float64:
+            raise ValueError(f"ort::sampled_otf: every tensor must be float64 (got {t.dtype})")
+        if t.device != x.device:
+            raise ValueError(f"ort::sampled_otf: tensors on {x.device} and {t.device}")
+    if kind not in _OTF_KINDS:
+        raise ValueError(f"ort::sampled_otf: kind must be one of {list(_OTF_KINDS)} (got {kind!r})")
+    if x.dim() != 1 or y.shape != x.shape:
+        raise ValueError("ort::sampled_otf: x and y must be 1-D of one size")
+    if shift_x.dim() != 1 or shift_y.shape != shift_x.shape:
+        raise ValueError("ort::sampled_otf: shift_x and shift_y must be 1-D of one size")
+    n = x.numel()
+    batched = intensity.dim() == 2
+    if (intensity.dim() not in (1, 2) or opd_waves.shape != intensity.shape
+            or intensity.shape[-1] != n):
+        raise ValueError("ort::sampled_otf: intensity and opd_waves must both be (N,) or (B, N) "
+                         f"with N = {n} (got {tuple(intensity.shape)} and "
+                         f"{tuple(opd_waves.shape)})")
+    if coeffs.dim() != intensity.dim() or (batched and coeffs.shape[0] != intensity.shape[0]):
+        raise ValueError("ort::sampled_otf: coeffs must be (T,) for unbatched and (B, T) for "
+                         f"batched pupils (got {tuple(coeffs.shape)})")
+    b = intensity.shape[0] if batched else 1
+    return b, n, coeffs.shape[-1], shift_x.numel(), batched
+
+
+def _otf_shape(b, f, batched):
+    return (b, f, 2) if batched else (f, 2)
+
+
+@torch.library.custom_op("ort::sampled_otf", mutates_args=(), device_types="cuda")
+def sampled_otf(x: torch.Tensor, y: torch.Tensor, intensity: torch.Tensor,
+                opd_waves: torch.Tensor, coeffs: torch.Tensor, kind: str,
+                shift_x: torch.Tensor, shift_y: torch.Tensor) -> torch.Tensor:
+    """ort_sampled_otf on the current stream: otf[b, f] = sum_j [r <= 1] I_bj exp(2 pi i (opd_bj
+    - W_b(x_j - shift_x[f], y_j - shift_y[f]))) as (re, im), W_b the polynomial of scheme
+    `kind` with coefficients coeffs[b] -- every frequency and batch entry in one launch pair,
+    no host synchronisation. (N,) pupils give [F, 2], (B, N) pupils [B, F, 2]. Forward only: a
+    requires_grad input raises NotImplementedError."""
+    from .raytrace import _stream_handle
+
+    lib = _native.load()
+    b, n, t, f, batched = _check_sampled_otf_inputs(x, y, intensity, opd_waves, coeffs, kind,
+                                                    shift_x, shift_y)
+    terms, radial = _otf_terms(kind, t, x.device)
+    out = torch.empty(_otf_shape(b, f, batched), dtype=torch.float64, device=x.device)
+    size = int(lib.ort_sampled_otf_workspace_size(b, f, n))
+    _native.check(size if size < 0 else 0, "ort_sampled_otf_workspace_size")
+    ws = torch.empty(max(size, 8), dtype=torch.uint8, device=x.device)
+    args = [v.detach().contiguous() for v in (x, y, intensity, opd_waves, coeffs, shift_x,
+                                              shift_y)]
+    rc = lib.ort_sampled_otf(addr(args[0]), addr(args[1]), n, addr(args[2]), addr(args[3]), b,
+                             addr(terms), addr(radial), addr(args[4]), t, addr(args[5]),
+                             addr(args[6]), f, addr(out), addr(ws), size, _stream_handle())
+    _native.check(rc, "ort_sampled_otf")
+    return out
+
+
+@sampled_otf.register_kernel("cpu")
+def _sampled_otf_cpu(x, y, intensity, opd_waves, coeffs, kind, shift_x, shift_y):
+    """The CPU dispatch key: the same term and summation order in the host library."""
+    from . import host
+
+    b, n, t, f, batched = _check_sampled_otf_inputs(x, y, intensity, opd_waves, coeffs, kind,
+                                                    shift_x, shift_y)
+    terms, radial = _otf_terms(kind, t, "cpu")
+    args = [v.detach().contiguous() for v in (x, y, intensity, opd_waves, coeffs, shift_x,
+                                              shift_y)]
+    return host.sampled_otf(args, b, t, terms, radial).reshape(_otf_shape(b, f, batched))
+
+
+@sampled_otf.register_fake
+def _(x, y, intensity, opd_waves, coeffs, kind, shift_x, shift_y):
+    b, _, _, f, batched = _check_sampled_otf_inputs(x, y, intensity, opd_waves, coeffs, kind,
+                                                    shift_x, shift_y)
+    return x.new_empty(_otf_shape(b, f, batched), dtype=torch.float64)
+
+
+_SAMPLED_OTF_NO_GRAD = ("ort::sampled_otf is not differentiable: autograd through the Zernike "
+                        "fit and the pupil shear is not implemented (detach the inputs)")
+
+
+def _sampled_otf_setup(ctx, inputs, output):
+    # refuse in the forward, as ort::huygens_psf does
+    if any(ctx.needs_input_grad):
+        raise NotImplementedError(_SAMPLED_OTF_NO_GRAD)
+
+
+def _sampled_otf_backward(ctx, grad):
+    raise NotImplementedError(_SAMPLED_OTF_NO_GRAD)
+
+
+sampled_otf.register_autograd(_sampled_otf_backward, setup_context=_sampled_otf_setup)
 
 
 # --------------------------------------------------------------------------------------

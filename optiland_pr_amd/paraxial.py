@@ -123,6 +123,14 @@ class Paraxial:
         loc_relative = -y[-1] / u[-1]
         return loc_relative[0]
 
+    # -- paraxial.py:297-314 --
+    def XPD(self):
+        """The exit pupil diameter: twice the marginal ray's height propagated from the image
+        surface to the exit pupil."""
+        ya, ua = self.marginal_ray()
+        yxp = ya[-1] + ua[-1] * self.XPL()
+        return 2 * yxp[0]
+
     # -- paraxial.py:387-417 --
     def marginal_ray(self):
         EPD = self.EPD()
