@@ -1197,10 +1197,141 @@ DIST_CASES = [("random", 1000, {"seed": 7}), ("uniform", 33, {}), ("uniform", 12
               ("positive_line_y", 10, {}), ("cross", 21, {}), ("cross", 20, {})]
 
 
+HV_POLYGON = (np.array([-1.5, 1.5, 1.5, 1.5, -0.5, -0.5, -1.5]),
+              np.array([-1.0, -1.0, 0.0, 0.0, 0.0, 2.0, 2.0]))
+
+
+def _aperture_primitives(d, out):
+    """The primitives (to_dict() records) of an aperture's to_dict() tree, in program order."""
+    if "a" in d and isinstance(d["a"], dict):
+        _aperture_primitives(d["a"], out)
+        _aperture_primitives(d["b"], out)
+    else:
+        out.append(d)
+    return out
+
+
+def _edge_points(dicts):
+    """The points of one aperture at which a clip can go wrong, from its to_dict(): base
+    points on every primitive's boundary, each followed by its four nextafter neighbours
+    (one step in -x, +x, -y, +y), then signed zeros and the three non-finite points."""
+    prims = _aperture_primitives(dicts, [])
+    n_ang = 64 if len(prims) <= 4 else 12
+    ang = 2.0 * np.pi * (np.arange(n_ang) + 0.25 * (np.arange(n_ang) % 3)) / n_ang
+    # directions whose squares sum to 1 up to rounding: the axes and three Pythagorean triples
+    dirs = [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)]
+    for a, b, c in ((3, 4, 5), (5, 12, 13), (8, 15, 17)):
+        dirs += [(a / c, b / c), (-b / c, a / c), (-a / c, -b / c), (b / c, -a / c)]
+    ux = np.concatenate((np.cos(ang), [p[0] for p in dirs]))
+    uy = np.concatenate((np.sin(ang), [p[1] for p in dirs]))
+    base = []
+    axes = []  # coordinate values paired with signed zeros below
+    for p in prims:
+        t = p["type"]
+        if t in ("RadialAperture", "OffsetRadialAperture"):
+            ox, oy = float(p.get("offset_x", 0.0)), float(p.get("offset_y", 0.0))
+            for r in (float(p["r_max"]), float(p["r_min"])):
+                if r > 0:
+                    base.append(np.column_stack((ox + r * ux, oy + r * uy)))
+            base.append(np.array([[ox, oy]]))
+            axes += [float(p["r_max"]), -float(p["r_max"])]
+        elif t == "EllipticalAperture":
+            ox, oy = float(p["offset_x"]), float(p["offset_y"])
+            base.append(np.column_stack((ox + float(p["a"]) * ux, oy + float(p["b"]) * uy)))
+            axes += [float(p["a"]), -float(p["b"])]
+        elif t == "RectangularAperture":
+            x0, x1, y0, y1 = (float(p[k]) for k in ("x_min", "x_max", "y_min", "y_max"))
+            f = np.linspace(0.0, 1.0, 9)
+            xs, ys = x0 + f * (x1 - x0), y0 + f * (y1 - y0)
+            xs[-1], ys[-1] = x1, y1
+            for yv in (y0, y1):
+                base.append(np.column_stack((xs, np.full(9, yv))))
+            for xv in (x0, x1):
+                base.append(np.column_stack((np.full(9, xv), ys)))
+            axes += [x0, x1, y0, y1]
+        elif t == "PolygonAperture":
+            vx, vy = np.asarray(p["x"], dtype=np.float64), np.asarray(p["y"], dtype=np.float64)
+            base.append(np.column_stack((vx, vy)))
+            nx, ny = np.roll(vx, -1), np.roll(vy, -1)
+            for f in (0.5, 0.25):  # edge midpoints and quarter points
+                base.append(np.column_stack((vx + f * (nx - vx), vy + f * (ny - vy))))
+            # the even-odd test's tie case: at the height of each vertex, left and right of
+            # every vertex's x
+            for d in (-0.5, 0.5, -7.0, 7.0):
+                gx, gy = np.meshgrid(vx + d, vy)
+                base.append(np.column_stack((gx.ravel(), gy.ravel())))
+            axes += [float(vx.min()), float(vy.max())]
+        else:
+            raise ValueError(t)
+    base = np.concatenate(base)
+    inf = np.inf
+    pts = np.stack((base,
+                    np.column_stack((np.nextafter(base[:, 0], -inf), base[:, 1])),
+                    np.column_stack((np.nextafter(base[:, 0], inf), base[:, 1])),
+                    np.column_stack((base[:, 0], np.nextafter(base[:, 1], -inf))),
+                    np.column_stack((base[:, 0], np.nextafter(base[:, 1], inf)))),
+                   axis=1).reshape(-1, 2)
+    zeros = [(a, b) for a in (0.0, -0.0) for b in (0.0, -0.0)]
+    for v in dict.fromkeys(axes):
+        zeros += [(0.0, v), (-0.0, v), (v, 0.0), (v, -0.0)]
+    tail = np.array(zeros + [(np.nan, 0.0), (0.0, np.nan), (np.inf, 0.0)])
+    return np.concatenate((pts, tail))
+
+
+def aperture_edge_goldens(aps):
+    """contains(x, y) of every reference aperture -- the nine of apertures.npz, a
+    right-nested union of 32 disjoint offset discs (a stack 32 deep), a left-nested chain of
+    differences, and a polygon with a horizontal edge, a vertical edge and a repeated vertex
+    -- on its own boundary points (_edge_points: circles and ellipses at 64 skewed angles
+    (12 with more than four primitives), the axes and Pythagorean directions; rectangle
+    edges and corners; polygon vertices, edge mid and quarter points and the points at every
+    vertex's height), each with its four one-ulp neighbours, then signed zeros and (NaN, 0),
+    (0, NaN), (inf, 0) -> tests/golden/aperture_edges.npz as <name>/x, <name>/y,
+    <name>/mask, with the apertures' to_dict() in aperture_edges.json.
+
+    Every mask, the non-finite points' included, is the reference's own contains(): its
+    polygon backend (matplotlib's Path.contains_points) does not raise on them."""
+    from optiland.physical_apertures import (
+        EllipticalAperture,
+        OffsetRadialAperture,
+        PolygonAperture,
+        RectangularAperture,
+    )
+
+    aps = dict(aps)
+    discs = [OffsetRadialAperture(0.4, 0, -3.5 + i, -1.5 + j) for j in range(4) for i in range(8)]
+    u = discs[-1]
+    for d in discs[-2::-1]:
+        u = d | u
+    aps["union32"] = u
+    c = RectangularAperture(-4.0, 4.0, -3.0, 3.0)
+    for b in (OffsetRadialAperture(1.5, 0, -4.0, 0.0),       # across the left edge
+              EllipticalAperture(2.0, 0.75, 1.0, 3.0),       # across the top edge
+              RectangularAperture(3.0, 5.0, -4.0, -2.0),     # across a corner
+              OffsetRadialAperture(1.0, 0.5, 0.5, -0.5),     # a ring inside
+              RectangularAperture(0.0, 1.0, -1.0, 0.0),      # overlaps the ring
+              PolygonAperture(*HV_POLYGON)):
+        c = c - b
+    aps["difference_chain"] = c
+    aps["polygon_hv"] = PolygonAperture(*HV_POLYGON)
+    out, dicts = {}, {}
+    for name, ap in aps.items():
+        dicts[name] = json.loads(json.dumps(ap.to_dict(), default=lambda o: np.asarray(o).tolist()))
+        pts = _edge_points(dicts[name])
+        out[f"{name}/x"] = pts[:, 0].copy()
+        out[f"{name}/y"] = pts[:, 1].copy()
+        with np.errstate(invalid="ignore"):
+            out[f"{name}/mask"] = np.asarray(ap.contains(out[f"{name}/x"], out[f"{name}/y"]),
+                                             dtype=bool)
+    np.savez_compressed(os.path.join(HERE, "aperture_edges.npz"), **out)
+    with open(os.path.join(HERE, "aperture_edges.json"), "w") as f:
+        json.dump(dicts, f, indent=1)
+
+
 def aperture_goldens():
-    """contains(x, y) of every reference aperture kind on 6000 points (random, a grid
+    """contains(x, y) of every reference aperture kind on 5449 points (random, a grid
     through the vertices, the vertices themselves) -> tests/golden/apertures.npz, with
-    the apertures' to_dict() in apertures.json."""
+    the apertures' to_dict() in apertures.json; then aperture_edge_goldens."""
     from optiland.physical_apertures import (
         EllipticalAperture,
         OffsetRadialAperture,
@@ -1236,6 +1367,7 @@ def aperture_goldens():
     np.savez_compressed(os.path.join(HERE, "apertures.npz"), **out)
     with open(os.path.join(HERE, "apertures.json"), "w") as f:
         json.dump(dicts, f, indent=1)
+    aperture_edge_goldens(aps)
 
 
 def distribution_goldens():

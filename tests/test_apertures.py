@@ -1,7 +1,10 @@
 """Physical apertures (CPU): the native classes, lowered to aperture programs and
 evaluated by the oracle, against the reference's own contains() masks
-(tests/golden/apertures.npz / apertures.json from gen_golden.py --apertures); dict
-round trips; lowering flags."""
+(tests/golden/apertures.npz / apertures.json from gen_golden.py --apertures, and the
+boundary points of aperture_edges.npz / aperture_edges.json); the host build's clip
+(csrc/ort_core.h clip_radial and aperture_contains, called from the surface step of
+csrc/ort_host.cpp) on the same points, mask for mask (tests/_apertures.py); dict round
+trips; lowering flags."""
 
 import json
 import os
@@ -20,6 +23,7 @@ from optiland_pr_amd.apertures import (
     RectangularAperture,
     program_depth,
 )
+from tests import _apertures as A
 from tests.conftest import REPO, load_golden
 
 NAMES = ("radial", "offset_radial", "ellipse", "rect", "polygon", "union", "intersection",
@@ -38,6 +42,82 @@ def test_contains_matches_reference(golden, name):
     ap = BaseAperture.from_dict(dicts[name])
     got = trace_np.aperture_contains(ap.program(), g["x"], g["y"])
     assert np.array_equal(got, g[name]), (name, int(np.sum(got != g[name])))
+
+
+@pytest.mark.parametrize("name", A.EDGE_NAMES)
+def test_contains_matches_reference_at_edges(name):
+    """The oracle on every aperture's own boundary points, their one-ulp neighbours, signed
+    zeros and the non-finite points: equal to the reference's contains() everywhere."""
+    ap, x, y, mask = A.case(f"edge/{name}")
+    got = A.expected(ap, x, y)
+    assert np.array_equal(got, mask), (name, np.flatnonzero(got != mask)[:8].tolist())
+    assert 0 < mask.sum() < mask.size and not mask[-3:].any()  # the non-finite points are out
+
+
+def test_edge_fixture_shapes():
+    """What the boundary fixture must hold for the programs it is there to break: a stack
+    32 deep, a chain of differences, points inside exactly one disc of the union for every
+    disc (every bit of the stack mask decides some point)."""
+    ap, x, y, mask = A.case("edge/union32")
+    prog = ap.program()
+    assert program_depth(prog) == 32 and prog[-31:] == [_abi.AP_UNION] * 31
+    for k in range(32):
+        ox, oy = prog[5 * k + 3], prog[5 * k + 4]
+        assert mask[(x == ox) & (y == oy)].all() and np.any((x == ox) & (y == oy))
+    chain = A.case("edge/difference_chain")[0]
+    for _ in range(6):  # left-nested: ((((((a - b1) - b2) - b3) - b4) - b5) - b6)
+        assert type(chain).__name__ == "DifferenceAperture"
+        chain = chain.a
+    assert type(chain) is RectangularAperture
+    assert program_depth(A.case("edge/difference_chain")[0].program()) == 2
+    hv = A.case("edge/polygon_hv")[0]
+    pts = list(zip(hv.x.tolist(), hv.y.tolist(), strict=True))
+    assert len(set(pts)) == len(pts) - 1  # one repeated vertex
+    assert np.any(np.diff(hv.x) == 0) and np.any(np.diff(hv.y) == 0)
+
+
+@pytest.mark.parametrize("family", A.FAMILIES)
+@pytest.mark.parametrize("cid", A.CASES)
+def test_host_build_clip(cid, family):
+    """The host build's clip on both fixtures through host.trace_sequential, in front of
+    each family's lens: mask, intensity bits and x, y (A.check)."""
+    ap, x, y, mask = A.case(cid)
+    exp = mask if family != "decentred" else A.expected(ap, x, y, family)
+    out = A.host_trace(A.table_of(A.lens(ap, family)), x, y)
+    A.check(out, *A.expected_xy(x, y, family), exp, f"host {family} {cid}")
+
+
+@pytest.mark.parametrize("cid", A.CASES)
+def test_host_build_clip_other_entries(cid):
+    """The same through the host build's per-ray-wavelength, recording and polarized
+    entries: the record of the aperture surface carries the clipped intensity and x, y."""
+    ap, x, y, mask = A.case(cid)
+    o = A.lens(ap)
+    ex, ey = A.expected_xy(x, y)
+    A.check(A.host_trace(A.table_of(o), x, y, w=A.per_ray_wavelengths(x.size)), ex, ey, mask,
+            f"host per-ray w {cid}")
+    A.check(A.host_trace(A.table_of(o, polarized=True), x, y, polarized=True), ex, ey, mask,
+            f"host polarized {cid}")
+    out = A.host_trace(A.table_of(o, record=[0]), x, y, record=True)
+    A.check(out, ex, ey, mask, f"host recording {cid}")
+    rec = out["rec"]
+    assert rec.shape == (1, 8, x.size)
+    A.check({"x": rec[0, 0], "y": rec[0, 1], "i": rec[0, 6]}, ex, ey, mask, f"host record {cid}")
+
+
+def test_depth_33_is_refused():
+    """A stack 33 deep does not fit the kernels' 32-bit mask: refused at lowering."""
+    from optiland_pr_amd.apertures import OffsetRadialAperture
+
+    discs = [OffsetRadialAperture(0.1, 0, float(k), 0.0) for k in range(33)]
+    u = discs[-1]
+    for d in discs[-2::-1]:
+        u = d | u
+    assert program_depth(u.program()) == 33
+    with pytest.raises(ValueError, match="nests too deeply"):
+        A.table_of(A.lens(u))
+    assert program_depth(u.b.program()) == 32
+    A.table_of(A.lens(u.b))  # 32 lowers
 
 
 @pytest.mark.parametrize("name", NAMES)
